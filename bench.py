@@ -12,7 +12,13 @@ sfm_match_batch_l2_f32), inputs resident in HBM, launch sets pipelined over PIPE
 its own pairs (the path shards by image pair) and the pairs' match records are exchanged by one RCCL
 all-gather per EXCH_BATCH pairs (sfm_mvs_amd.sharded.BatchedExchange), inside the timed region.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events around the dominant
+Prints ONE JSON line on rank 0.  A plain run of the default workload sets up, warms up, times the K steps and prints the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`); everything else it can measure
+needs `--full`:
+  python bench.py --gpus 1 --steps K --warmup W --full                # + cold figure, roofline, latency / variant legs, other workloads, CPU baseline
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    # + the last timed step's results as DIR/<name>.npy
+
+With --full, `roofline` is measured live with HIP events around the dominant
 kernel (knn_filter_split2_kernel, v_mfma_f32_32x32x16_f16) via the library's sfm_profile_* hook, on
 steps run after the timed region;
 `cpu_baseline` times the CPU oracle (a port of OpenCV's batchDistance semantics) on a bounded
@@ -56,8 +62,13 @@ def parse():
     ap.add_argument("--nt", type=int, default=10000)
     ap.add_argument("--images", type=int, default=None, help="workload c5: images in the sequence IN TOTAL (default 256 = BASELINE config 5); workload allpairs: images (default 64)")
     ap.add_argument("--verify-images", type=int, default=6, help="workload allpairs: essential-matrix RANSAC + recoverPose (isfm.py:80-94) on the pairs among the first N images")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also measure everything beside the headline (cold figure, live roofline, latency and variant legs, "
+                         "the other workloads, the CPU baseline; at N > 1 configs[4]); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload, one rank: write what the last timed step computed (its pairs' KNN and Lowe results) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other workloads and the variant legs")
     ap.add_argument("--pipe-depth", type=int, default=None, help=f"launch sets (knn: default {PIPE_DEPTH}) / frames (sift: default {SIFT_DEPTH}) in flight per GPU (1 = one stream)")
     ap.add_argument("--pair-batch", type=int, default=PAIR_BATCH, help="independent pairs per launch set (1..8)")
     ap.add_argument("--from-pixels", action="store_true",
@@ -66,7 +77,12 @@ def parse():
     ap.add_argument("--dry-run-dist", action="store_true",
                     help="no GPU: run the N-rank launch, rendezvous, batched all-gather and timing protocol of the knn / c5 legs on CPU tensors over gloo "
                          "(the slots are filled with a rank-stamped pattern instead of KNN blocks); the JSON line carries dry_run: true and no throughput")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "knn" or args.gpus != 1 or args.dry_run_dist):
+        ap.error("--dump-outputs: the default workload on one GPU only")
+    return args
 
 
 def self_launch(args):
@@ -172,7 +188,7 @@ def main():
     if args.workload == "knn":
         out = bench_knn(args, world, rank, dev)
         multi = world > 1 or bool(os.environ.get("SFM_BENCH_EXCHANGE"))       # (the env switch: the N > 1 code path on one rank, dev / test)
-        if rank == 0 and not multi:
+        if rank == 0 and not multi and args.full:
             if not args.no_extras:
                 out["extra"] = extras(dev)
                 out["extra"]["config4"] = extra_c4(dev)
@@ -202,8 +218,8 @@ def main():
                     "note": "the other legs of this same run (details under `extra`, `sift_like`, `fp16_body_variant`); frames of the sfm legs are SURROGATES of the Gustav photographs"}
             if not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_knn_baseline(args.nq, args.nt, 0, 1)
-        elif multi and not args.no_extras:
-            # The driver's scaling command (`bench.py --gpus N`, N > 1): the headline stays config 2, weak-scaled (so that the N = 1 point of
+        elif multi and args.full and not args.no_extras:
+            # `bench.py --gpus N --full`, N > 1: the headline stays config 2, weak-scaled (so that the N = 1 point of
             # SCALE equals BENCH), and the SAME run also measures BASELINE configs[4] — 256 images x 50k descriptors, the 255 sequential
             # pairs split over the N ranks (+ one halo image each), both all-gathers (match records, triangulated points) over the
             # RCCL group — reported under config.secondary.  Every rank takes part (collectives).

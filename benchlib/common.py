@@ -114,6 +114,25 @@ def cpu_knn_baseline(nq, nt, seed_q, seed_t):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, bm, n):
+    """--dump-outputs: the results of the first `n` pairs of BatchMatcher `bm`'s last launch set, as its caller receives them,
+    one .npy per array under `path`.  Indices are stored as float64 (exact); slots past a pair's survivor count hold -1."""
+    count = bm.count[:n, 0].cpu().numpy()
+    keep = np.arange(bm.nq)[None, :] < count[:, None]
+    arrays = {"knn_train_idx": bm.idx[:n].cpu().numpy().astype(np.float64),             # [pair, query, 2 nearest]
+              "knn_distance": bm.dist[:n].cpu().numpy(),                                  # float32, same shape
+              "ratio_count": count.astype(np.float64),                                    # [pair]: Lowe survivors
+              "ratio_query_idx": np.where(keep, bm.out_q[:n].cpu().numpy(), -1).astype(np.float64),   # [pair, slot]
+              "ratio_train_idx": np.where(keep, bm.out_t[:n].cpu().numpy(), -1).astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def knn_source_hash():
     """sha256 of the csrc/knn.hip CODE the LOADED library was built from (sfm_build_id(): baked in at build time; comments and
     whitespace do not count): what the PMC traffic stamps under profiles/ must carry to be reported."""

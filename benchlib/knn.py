@@ -33,6 +33,8 @@ def bench_knn(args, world, rank, dev):
         # buffers alternate.
         from sfm_mvs_amd import sharded
         ex = sharded.BatchedExchange((2, nq, 2), torch.int32, dev, batch=EXCH_BATCH, nbuf=depth + 1)   # a launch set waits for the gather `depth + 1` sets back: all `depth` streams stay busy
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: one rank without the exchange only (the exchange writes the results into its own buffers)")
 
     step_no = [0]
 
@@ -70,16 +72,18 @@ def bench_knn(args, world, rank, dev):
     # (3) streams that the runtime really serves concurrently (see PIPE_DEPTH): probe, replace, keep the fastest (one rank only: with an
     # exchange in the loop the ranks would have to agree on the collectives the probe issues)
     stream_probe_ms = pipe.tune_streams(sets, tries=STREAM_TRIES) if depth > 1 and ex is None else []
-    # COLD figure: the same K steps right after an idle period, before the clock ramp (kernels and streams are loaded, the
-    # device is not at its sustained clock) — what a caller that matches one batch now and then sees.
-    time.sleep(0.5)
-    barrier_sync(world)
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step()
-    drain()
-    barrier_sync(world)
-    cold_elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if args.full:
+        # COLD figure: the same K steps right after an idle period, before the clock ramp (kernels and streams are loaded, the
+        # device is not at its sustained clock) — what a caller that matches one batch now and then sees.
+        time.sleep(0.5)
+        barrier_sync(world)
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            step()
+        drain()
+        barrier_sync(world)
+        cold_elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
+        step_no[0] -= args.steps                             # the timed steps see the same images with and without --full
     for i in range(CLOCK_WARMUP_STEPS):                      # (a fixed count: every rank issues the same collectives)
         step()
         if i % 16 == 15:
@@ -101,6 +105,48 @@ def bench_knn(args, world, rank, dev):
     elapsed = max_over_ranks(elapsed, world, dev)
     exchange_ms = ex.exchange_ms() if ex is not None else None       # device time inside the timed region's collectives
     exchange_calls = ex.collectives if ex is not None else 0
+    if args.dump_outputs:
+        # what the last timed step handed its caller: launch set i's results live in matcher i % depth (ops.BatchPipeline)
+        dump_outputs(args.dump_outputs, pipe.matchers[(pipe.n - 1) % depth], pbatch)
+    stats = pm.stats[0].cpu().tolist()
+    value = world * pbatch * nq * nt * args.steps / elapsed      # every step matches pbatch pairs per GPU
+    algo_flop = pbatch * nq * nt * FLOP_PER_DISTANCE        # one filter launch covers the whole pair batch
+    pair_flop = nq * nt * FLOP_PER_DISTANCE                 # ... a single-pair launch (the variant legs below) one pair
+    mode = stats[3]
+    int_body = mode in (4, 5)        # v_mfma_i32_32x32x32_i8: exact u8 data (4) or float data QUANTISED to 8 bits (5) — priced against the int8 roof
+    mode_name = {0: "fp16 single product (inputs exact in fp16)", 1: "fp16 single product", 2: "bf16 hi+mid split (3 products)",
+                 3: "fp32 MFMA", 4: "exact-integer i8 MFMA (u8-integer descriptors)",
+                 5: "i8 MFMA on the descriptors QUANTISED to 8 bits (one grid per pair; the certificate uses the measured residual norms)"}.get(mode, str(mode))
+    out = {
+        "metric": "descriptor-pair distances/sec (BF-KNN k=2 + Lowe ratio)", "value": value, "unit": "distances/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "ms_per_pair": elapsed / (args.steps * pbatch) * 1e3, "host_enqueue_ms_per_step": t_enq / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": f"f32 results (bit-identical to the direct-form f32 reference); filter arithmetic on MFMA: {mode_name}; "
+                 "f32 exact refine",
+        "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[1]: 10k x 10k uniform[0,1) float32 128-D descriptors, BF-KNN k=2 + "
+                               f"Lowe ratio 0.70; a step = one launch set = a batch of {pbatch} distinct pairs of that shape per GPU "
+                               f"({pbatch}e8 distances; {pbatch} distinct pairs per launch set, {N_SETS} sets of images rotating over the steps)",
+                   "nq": nq, "nt": nt, "dim": 128, "pairs_per_step": pbatch, "distinct_pairs_per_launch_set": pbatch, "image_sets": N_SETS,
+                   "parallelism": f"pair-sharded x{world}" + (f" + one RCCL all-gather of the match records per {EXCH_BATCH} pairs" if world > 1 else "")
+                                  + f"; independent pairs issued {pbatch} per launch set (sfm_match_batch_l2_f32), {depth} launch sets in flight per GPU (one HIP stream each)",
+                   "pairs_per_launch": pbatch,
+                   "stream_probe_ms_per_launch_set": stream_probe_ms,
+                   "stream_probe_note": f"set-up, untimed: the pipeline's {depth} streams are probed and replaced up to {STREAM_TRIES - 1} times, the fastest set is kept "
+                                        "(two launch sets overlap fully only when the runtime serves their streams concurrently: ~1 fresh pair in 24 does not)",
+                   "setup": f"streams and kernels loaded, then {CLOCK_WARMUP_STEPS} untimed steps of the same workload (~60 ms: the device reaches its sustained clock) before the W warm-up steps"},
+        "knn_stats": {"rescanned_queries": stats[0], "filter_workgroups": stats[1], "streams_per_query": stats[2],
+                      "filter_mode": mode_name},
+    }
+    if ex is not None:
+        out["exchange"] = {"ms_total_in_timed_region": exchange_ms, "ms_per_step": exchange_ms / args.steps, "ms_per_pair": exchange_ms / (args.steps * pbatch),
+                           "collectives_since_start": exchange_calls, "pairs_per_collective": EXCH_BATCH,
+                           "bytes_per_rank_per_collective": EXCH_BATCH * nq * 16,
+                           "note": "device time between the events bracketing each all_gather_into_tensor on the issuing stream "
+                                   "(includes waiting for the batch's producers); the pair kernels of the next batch overlap it"}
+    if not args.full:
+        return out
     # Roofline sampling, AFTER the timed region: the library brackets its kernels with HIP events on the launch stream
     # when profiling is on.  An event pair costs ~3.5 us of stream time, and with several pairs in flight a kernel's
     # event-to-event time also contains the neighbours' kernels it shares the chip with — so the sampled steps run
@@ -126,8 +172,6 @@ def bench_knn(args, world, rank, dev):
         torch.cuda.synchronize()
     ops.profile_read(0)
     ref_ms, ref_n = ops.profile_read(1)
-    stats = pm.stats[0].cpu().tolist()
-
     # HBM-side bytes per launch of the dominant kernel come from PMC passes (rocprofv3 cannot be driven from inside the
     # process); the committed figure is stamped with the sha256 of the kernel source it was measured on and is
     # reported only while that source is unchanged.
@@ -139,15 +183,10 @@ def bench_knn(args, world, rank, dev):
             traffic, traffic_note = tj.get("bytes_per_launch"), f"profiles/knn_traffic.json ({tj.get('source')})"
         else:
             traffic_note = "profiles/knn_traffic.json is stale (csrc/knn.hip or the pair batch changed since the PMC passes): not reported"
-    value = world * pbatch * nq * nt * args.steps / elapsed      # every step matches pbatch pairs per GPU
     filt_avg_ms = filt_ms / max(filt_n, 1)
-    algo_flop = pbatch * nq * nt * FLOP_PER_DISTANCE        # one filter launch covers the whole pair batch
-    pair_flop = nq * nt * FLOP_PER_DISTANCE                 # ... a single-pair launch (the variant legs below) one pair
     achieved = algo_flop / (filt_avg_ms * 1e-3) / 1e12
     # MFMA work actually issued by the filter arithmetic the device chose (stats[3]): one fp16 product per fp32 product
     # (8 MFMAs per 32x32x128 tile) or the 3-product bf16 split (24)
-    mode = stats[3]
-    int_body = mode in (4, 5)        # v_mfma_i32_32x32x32_i8: exact u8 data (4) or float data QUANTISED to 8 bits (5) — priced against the int8 roof
     mfma_per_tile = {0: 8, 1: 8, 2: SPLIT_MFMA_PER_TILE}.get(mode, 8)
     # (+ the accumulator-init MFMA of every tile, v_mfma_f32_32x32x8_bf16: half the flops of a product MFMA)
     issued = pbatch * (nq / 32.0) * (nt / 32.0) * (mfma_per_tile + 0.5) * 2 * 32 * 32 * 16 / (filt_avg_ms * 1e-3) / 1e12
@@ -155,32 +194,11 @@ def bench_knn(args, world, rank, dev):
         issued = pbatch * (nq / 32.0) * (nt / 32.0) * (4 + 1.0 / 8) * 2 * 32 * 32 * 32 / (filt_avg_ms * 1e-3) / 1e12
     peak_hl, unit_hl, sus_hl = ((I8_MFMA_PEAK_TOPS, "TOP/s", I8_MFMA_SUSTAINED_TOPS) if int_body
                                 else (BF16_MFMA_PEAK_TFLOPS, "TFLOP/s", F16_MFMA_SUSTAINED_TFLOPS))
-    mode_name = {0: "fp16 single product (inputs exact in fp16)", 1: "fp16 single product", 2: "bf16 hi+mid split (3 products)",
-                 3: "fp32 MFMA", 4: "exact-integer i8 MFMA (u8-integer descriptors)",
-                 5: "i8 MFMA on the descriptors QUANTISED to 8 bits (one grid per pair; the certificate uses the measured residual norms)"}.get(mode, str(mode))
-    out = {
-        "metric": "descriptor-pair distances/sec (BF-KNN k=2 + Lowe ratio)", "value": value, "unit": "distances/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_pair": elapsed / (args.steps * pbatch) * 1e3, "host_enqueue_ms_per_step": t_enq / args.steps * 1e3,
-        "cold_value": world * pbatch * nq * nt * args.steps / cold_elapsed, "cold_ms_per_step": cold_elapsed / args.steps * 1e3,
-        "cold_note": "the same K steps timed after 0.5 s of idle, BEFORE the clock-ramp steps (kernels and streams loaded): `value` is the sustained rate, this the rate a cold device gives",
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": f"f32 results (bit-identical to the direct-form f32 reference); filter arithmetic on MFMA: {mode_name}; "
-                 "f32 exact refine",
-        "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[1]: 10k x 10k uniform[0,1) float32 128-D descriptors, BF-KNN k=2 + "
-                               f"Lowe ratio 0.70; a step = one launch set = a batch of {pbatch} distinct pairs of that shape per GPU "
-                               f"({pbatch}e8 distances; {pbatch} distinct pairs per launch set, {N_SETS} sets of images rotating over the steps)",
-                   "nq": nq, "nt": nt, "dim": 128, "pairs_per_step": pbatch, "distinct_pairs_per_launch_set": pbatch, "image_sets": N_SETS,
-                   "parallelism": f"pair-sharded x{world}" + (f" + one RCCL all-gather of the match records per {EXCH_BATCH} pairs" if world > 1 else "")
-                                  + f"; independent pairs issued {pbatch} per launch set (sfm_match_batch_l2_f32), {depth} launch sets in flight per GPU (one HIP stream each)",
-                   "pairs_per_launch": pbatch,
-                   "cold_value": world * pbatch * nq * nt * args.steps / cold_elapsed, "cold_ms_per_step": cold_elapsed / args.steps * 1e3,
-                   "cold_note": "`value` is the sustained rate; cold_value = the same K steps after 0.5 s of idle, before the clock ramp",
-                   "stream_probe_ms_per_launch_set": stream_probe_ms,
-                   "stream_probe_note": f"set-up, untimed: the pipeline's {depth} streams are probed and replaced up to {STREAM_TRIES - 1} times, the fastest set is kept "
-                                        "(two launch sets overlap fully only when the runtime serves their streams concurrently: ~1 fresh pair in 24 does not)",
-                   "setup": f"streams and kernels loaded, then {CLOCK_WARMUP_STEPS} untimed steps of the same workload (~60 ms: the device reaches its sustained clock) before the W warm-up steps"},
+    out.update({"cold_value": world * pbatch * nq * nt * args.steps / cold_elapsed, "cold_ms_per_step": cold_elapsed / args.steps * 1e3,
+                "cold_note": "the same K steps timed after 0.5 s of idle, BEFORE the clock-ramp steps (kernels and streams loaded): `value` is the sustained rate, this the rate a cold device gives"})
+    out["config"].update({"cold_value": world * pbatch * nq * nt * args.steps / cold_elapsed, "cold_ms_per_step": cold_elapsed / args.steps * 1e3,
+                          "cold_note": "`value` is the sustained rate; cold_value = the same K steps after 0.5 s of idle, before the clock ramp"})
+    out.update({
         "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak_hl, "unit": unit_hl,
                      "frac": achieved / peak_hl, "frac_of_sustained": achieved / sus_hl,
                      # the WHOLE step against the same roof: algorithmic work of a launch set / the timed region's time per step
@@ -202,16 +220,8 @@ def bench_knn(args, world, rank, dev):
                                         f"(pipeline drained); on those the kernel is launched {PROF_REPEAT}x back-to-back inside "
                                         "the event pair (idempotent) so that the event overhead (~7 us per pair) is amortised",
                      "note": "algorithmic = 256 FLOP per distance (SURVEY 8d); issued = MFMA flops of the arithmetic mode that ran"},
-        "kernels_ms": {"knn_filter": filt_avg_ms, "knn_refine": ref_ms / max(ref_n, 1)},
-        "knn_stats": {"rescanned_queries": stats[0], "filter_workgroups": stats[1], "streams_per_query": stats[2],
-                      "filter_mode": mode_name},
-    }
-    if ex is not None:
-        out["exchange"] = {"ms_total_in_timed_region": exchange_ms, "ms_per_step": exchange_ms / args.steps, "ms_per_pair": exchange_ms / (args.steps * pbatch),
-                           "collectives_since_start": exchange_calls, "pairs_per_collective": EXCH_BATCH,
-                           "bytes_per_rank_per_collective": EXCH_BATCH * nq * 16,
-                           "note": "device time between the events bracketing each all_gather_into_tensor on the issuing stream "
-                                   "(includes waiting for the batch's producers); the pair kernels of the next batch overlap it"}
+        "kernels_ms": {"knn_filter": filt_avg_ms, "knn_refine": ref_ms / max(ref_n, 1)}
+    })
     # latency of ONE pair launched alone (batch of one, one stream), and of one whole batch, outside the timed region
     pm = pm1 = ops.PairMatcher(nq, nt, dev, ratio=0.70)
     for _ in range(3):

@@ -287,8 +287,8 @@ def bench_dry_run(args, world, rank):
                       "exchange": {"collectives": ex.collectives, "pairs_per_collective": EXCH_BATCH, "ranks": dist.get_world_size(),
                                    "gathered_slots_verified": ok},
                       "launched_by": "bench.py self_launch" if os.environ.get("TORCHELASTIC_RUN_ID") else "external launcher"}}
-    if args.workload == "c5" or (args.workload == "knn" and world > 1):
-        # (default workload at N > 1: the real run measures BASELINE configs[4] beside the headline — main(); its partition is shown here)
+    if args.workload == "c5" or (args.workload == "knn" and world > 1 and args.full):
+        # (default workload at N > 1 with --full: the real run measures BASELINE configs[4] beside the headline — main(); its partition is shown here)
         n_img = max(2, args.images or 256)
         pairs = sharded.sequential_pairs(n_img)
         lo, hi = sharded.shard_range(len(pairs), world, rank)

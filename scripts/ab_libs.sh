@@ -19,6 +19,6 @@ for rep in 1 2; do for L in "$@"; do
   echo "== sift-like $L (rep $rep)"; SFM_WARM=20 stats $L python $R/scripts/run_knn_sift.py 60 8 1
 done; done
 for rep in 1 2; do for L in "$@"; do
-  echo "== bench $L"; SFM_HIP_LIB=$R/sfm_mvs_amd/lib/$L python $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+  echo "== bench $L"; SFM_HIP_LIB=$R/sfm_mvs_amd/lib/$L python $R/bench.py --steps 60 --warmup 10 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); s=d.get('sift_like',{}); print('value %.4g ms/step %.4f cold %.4g | sift-like %.4g ms/step %.4f | kernels' % (d['value'], d['ms_per_step'], d['cold_value'], s.get('distances_per_sec',0), s.get('ms_per_step',0)), d['kernels_ms'], s.get('kernels_ms'))"
 done; done

@@ -6,10 +6,10 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o knn -- python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o knn -- python $R/bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 cp $OUT/trace/knn_kernel_stats.csv $OUT/${TAG}_knn_kernel_stats.csv
 # the same bench with ONE pair in flight: kernel durations without the neighbouring pairs' kernels sharing the chip
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1 -o knn1 -- python $R/bench.py --steps 100 --warmup 10 --pipe-depth 1 --no-cpu-baseline --no-extras > $OUT/bench_depth1_under_rocprof.json 2>> $OUT/trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1 -o knn1 -- python $R/bench.py --steps 100 --warmup 10 --pipe-depth 1 --full --no-cpu-baseline --no-extras > $OUT/bench_depth1_under_rocprof.json 2>> $OUT/trace.log
 cp $OUT/trace1/knn1_kernel_stats.csv $OUT/${TAG}_knn_depth1_kernel_stats.csv
 # one launch set per step and nothing else (bench.py also launches single pairs for its latency and variant legs, which
 # mix into the averages above): the per-kernel durations of the batch the roofline is quoted on
@@ -61,7 +61,7 @@ cd $R
 # (round 6: stdout carries the compact line; the FULL record of a run is gpurun_out/bench_full.json — that is what is kept as rNN_bench_*.json,
 #  the line itself beside it as *.line)
 runb() { name=$1; shift; python bench.py "$@" > $OUT/${TAG}_bench_$name.line 2>> $OUT/trace.log; cp $R/gpurun_out/bench_full.json $OUT/${TAG}_bench_$name.json; }
-runb default --gpus 1 --steps 20 --warmup 5
+runb default --gpus 1 --steps 20 --warmup 5 --full
 cp $OUT/${TAG}_bench_default.json $OUT/${TAG}_bench_knn.json
 runb c5 --workload c5
 runb allpairs --workload allpairs
@@ -69,7 +69,7 @@ runb sfm --workload sfm --steps 3
 runb sfm_pixels --workload sfm --from-pixels --steps 3
 # launch sets in flight: the headline step at pipeline depth 1 .. 5 (bench.py's default is 2)
 for d in 1 2 3 4 5; do
-  python bench.py --steps 60 --warmup 10 --pipe-depth $d --no-cpu-baseline --no-extras 2>> $OUT/trace.log | python -c "
+  python bench.py --steps 60 --warmup 10 --pipe-depth $d --full --no-cpu-baseline --no-extras 2>> $OUT/trace.log | python -c "
 import sys, json; d = json.loads(sys.stdin.read()); print('pipe-depth $d: value %.4g distances/s  ms_per_step %.4f  frac_step %.3f' % (d['value'], d['ms_per_step'], d['roofline']['frac_step']))" >> $OUT/${TAG}_knn_pipe_depth.txt
 done
 # HIP API census of the from-pixels job (how often the host waits: hipStreamSynchronize / hipMemcpy / hipEventSynchronize)

@@ -1,7 +1,7 @@
 """Kernel timeline of the KNN step in steady state (two launch sets in flight): from a rocprofv3 --kernel-trace csv, the last N
 dispatches with start / end relative to the first, the queue they ran on, and per kernel the time it overlapped another queue's kernels.
-  cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o t -- python $R/bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline
-  python scripts/knn_timeline.py /tmp/tl/t_kernel_trace.csv [N]"""
+  rocprofv3 --kernel-trace --output-format csv -d <trace dir> -o t -- python bench.py --steps 40 --warmup 5 --full --no-extras --no-cpu-baseline
+  python scripts/knn_timeline.py <trace dir>/t_kernel_trace.csv [N]"""
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 40

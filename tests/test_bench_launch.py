@@ -22,13 +22,13 @@ def _run(*argv):
 
 
 def test_gpus_2_self_launches_two_ranks():
-    out, err = _run("--gpus", "2", "--dry-run-dist")
+    out, err = _run("--gpus", "2", "--dry-run-dist", "--full")
     assert out["n_gpus"] == 2 and out["dry_run"] is True and out["value"] is None
     ex = out["config"]["exchange"]
     assert ex["ranks"] == 2 and ex["gathered_slots_verified"] is True and ex["collectives"] >= 1
     assert out["config"]["launched_by"] == "bench.py self_launch"
     assert "launching 2 ranks" in err
-    # the default workload at N > 1 also runs BASELINE configs[4]: its partition rides in config.secondary —
+    # the default workload at N > 1 with --full also runs BASELINE configs[4]: its partition rides in config.secondary —
     # 255 sequential pairs (sfm.py:347) of 256 images split 128 / 127, every rank holding its images + ONE halo image
     sec = out["config"]["secondary"]
     assert sec["config5_images"] == 256 and sec["config5_pairs"] == 255 and sec["config5_pairs_per_rank"] == [128, 127]
@@ -47,6 +47,17 @@ def test_gpus_3_c5_partition_is_the_halo_split():
 def test_gpus_1_does_not_spawn():
     out, err = _run("--gpus", "1", "--dry-run-dist")
     assert out["n_gpus"] == 1 and "launching" not in err
+
+
+def test_plain_run_leaves_configs4_to_full():
+    out, _ = _run("--gpus", "2", "--dry-run-dist")
+    assert out["n_gpus"] == 2 and out["config"]["exchange"]["gathered_slots_verified"] is True and "secondary" not in out["config"]
+
+
+def test_rejects_empty_timed_region_and_dumps_outside_the_headline():
+    for argv in (["--steps", "0"], ["--warmup", "-1"], ["--workload", "tri", "--dump-outputs", "d"], ["--gpus", "2", "--dump-outputs", "d"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "error:" in r.stderr and r.stdout.strip() == "", (argv, r.stderr[-500:])
 
 
 def test_refuses_more_ranks_than_gpus():

@@ -1,6 +1,6 @@
-"""bench.py's output contract, as the driver reads it: exactly ONE JSON line on stdout with the metric of BASELINE.json, the
-whole-job value, the roofline of the dominant kernel measured live, and (default run) the CPU baseline.  Runs the real script
-with a handful of steps and without the extra legs."""
+"""bench.py's output contract, as the driver reads it: exactly ONE JSON line on stdout with the metric of BASELINE.json and the
+whole-job value; with --full also the roofline of the dominant kernel measured live and the CPU baseline.  Runs the real script
+with a handful of steps."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields(hip):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-extras", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -46,13 +46,14 @@ def _strict_loads(line):
 
 
 def test_driver_command_line_gives_one_short_strict_json_line(hip):
-    """The driver's own command, unmodified (BENCH_rNN.json: `python3 bench.py --gpus 1 --steps 20 --warmup 5`).  Round 5's line was 22.5 KB
+    """The driver's command of BENCH_rNN.json (`python3 bench.py --gpus 1 --steps 20 --warmup 5`) with `--full`, which keeps every leg of
+    those records (a plain run times the headline alone: test_plain_run_is_the_headline_alone).  Round 5's line was 22.5 KB
     and the driver, which keeps an 8 KB tail of stdout + stderr, could not parse it: the line must be short, strict JSON, alone
     on stdout, and stderr must stay small enough that the line survives in a combined 8 KB tail."""
     full = os.path.join(ROOT, "gpurun_out", "bench_full.json")
     if os.path.exists(full):
         os.remove(full)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                          capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -78,3 +79,42 @@ def test_driver_command_line_gives_one_short_strict_json_line(hip):
     # everything else went to the side file, itself strict JSON
     rec = _strict_loads(open(full).read())
     assert "extra" in rec and rec["value"] == pytest.approx(d["value"], rel=1e-6)
+
+
+def test_plain_run_is_the_headline_alone(hip, oracle, tmp_path):
+    """The plain command run for every change (`bench.py --gpus 1 --steps K --warmup W`): one strict JSON line with the headline fields,
+    exactly K timed steps, nothing measured beside them; --dump-outputs writes what the last timed step computed, equal to the oracle."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from benchlib.common import CLOCK_WARMUP_STEPS, DUMP_MAX_BYTES, N_SETS, PAIR_BATCH
+
+    K, W, dump = 4, 1, tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, [l[:200] for l in lines]
+    d = _strict_loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == K and d["warmup"] == W and d["higher_is_better"] is True
+    assert d["unit"] == "distances/s" and "distances/sec" in d["metric"] and "QUANTISED" in d["dtype"]
+    assert d["value"] == pytest.approx(PAIR_BATCH * 1e8 / (d["ms_per_step"] * 1e-3), rel=1e-6) and d["value"] > 1e12
+    assert not {"roofline", "cpu_baseline", "cold_value", "kernels_ms"} & set(d) and "secondary" not in d["config"]
+
+    a = {n: np.load(dump / f"{n}.npy") for n in ("knn_train_idx", "knn_distance", "ratio_count", "ratio_query_idx", "ratio_train_idx")}
+    assert sum(v.nbytes for v in a.values()) <= DUMP_MAX_BYTES and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["knn_train_idx"].shape == a["knn_distance"].shape == (PAIR_BATCH, 10000, 2) and a["ratio_query_idx"].shape == (PAIR_BATCH, 10000)
+    s = (CLOCK_WARMUP_STEPS + W + K - 1) % N_SETS                   # the image set of the last timed step (benchlib/knn.py: sets rotate per step)
+    rows = np.random.default_rng(0).choice(10000, 256, replace=False)
+    for b in range(PAIR_BATCH):
+        seed = 2 * (PAIR_BATCH * s + b)
+        q = torch.rand((10000, 128), generator=torch.Generator().manual_seed(seed)).numpy()
+        t = torch.rand((10000, 128), generator=torch.Generator().manual_seed(seed + 1)).numpy()
+        wi, wd = oracle.knn2(q[rows], t, nthreads=min(16, os.cpu_count() or 1))
+        assert np.array_equal(a["knn_train_idx"][b, rows], wi) and np.array_equal(a["knn_distance"][b, rows], wd), f"pair {b}"
+        wq, wt, _ = oracle.ratio_filter(a["knn_train_idx"][b].astype(np.int32), a["knn_distance"][b], 0.70)
+        m = int(a["ratio_count"][b])
+        assert m == len(wq) and np.array_equal(a["ratio_query_idx"][b, :m], wq) and np.array_equal(a["ratio_train_idx"][b, :m], wt)
+        assert (a["ratio_query_idx"][b, m:] == -1).all() and (a["ratio_train_idx"][b, m:] == -1).all()
