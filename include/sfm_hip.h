@@ -29,7 +29,8 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 3   /* 3 (round 6): + sfm_host_poll_count, sfm_debug_pnp_sweep_server; sfm_build_id() names every source file */
+#define SFM_ABI_VERSION 3   /* 3 (round 6): + sfm_host_poll_count, sfm_debug_pnp_sweep_server; sfm_build_id() names every source file;
+                               later, backward-compatible additions: sfm_mvs_plane_sweep, sfm_mvs_consistency */
 
 #define SFM_OK             0
 #define SFM_ERR_ARG       -1   /* null pointer, negative size, unsupported dim, misaligned pointer/stride */
@@ -517,6 +518,62 @@ int sfm_sift_detect_and_compute(const uint8_t* gray_dev, int64_t w, int64_t h, i
                                 double sigma, int64_t max_keypoints, float* keypoints_dev,
                                 float* descriptors_dev, int32_t* count_dev, void* ws, size_t ws_bytes,
                                 void* stream);
+
+/* ------------------------------------------------------------------------
+ * MVS  dense reconstruction                     sfm.py:298 (`densify = False`)
+ *      the cloud of to_ply's dense.ply branch   sfm.py:199
+ *
+ * The reference stops at the sparse cloud; these two entry points are the
+ * plane-sweep multi-view stereo that feeds `to_ply(..., densify=True)`
+ * (sfm_mvs_amd/mvs.py, docs/mvs.md).  Every step is a correctly rounded
+ * float32 operation in the order written here (no FMA, no reassociation), so
+ * an independent float32 restatement reproduces the outputs bit for bit.
+ *
+ * sfm_mvs_plane_sweep — the depth map of one reference view.
+ *   ref_dev    [h][w] uint8 reference gray frame; I' = (float)I - 128
+ *   src_dev    host array of nsrc DEVICE pointers, [h][w] uint8 source gray frames (same size), 1 <= nsrc <= 8
+ *   mv_host    host float32 [nsrc][12] = M (3x3 row-major) | v (3) per source, copied into the kernel arguments:
+ *              pixel (x, y) of plane j maps to h_i = ((M_i0*x + M_i1*y) + M_i2) + v_i*invd[j]; valid iff h_2 > 0,
+ *              0 <= px = h_0/h_2 <= w-1 and 0 <= py = h_1/h_2 <= h-1; x0 = min(floor(px), w-2), fx = px - x0 (same in y);
+ *              val = (1-fy)*((1-fx)*I'00 + fx*I'01) + fy*((1-fx)*I'10 + fx*I'11)
+ *   invd_dev   [ndepth] float32 inverse depths of the fronto-parallel planes (caller-owned, > 0), 2 <= ndepth <= 1024
+ *   radius     1..4: the window is (2r+1)^2 pixels about (x, y), n = (float)(2r+1)^2; 2r+1 <= w, h <= 32767
+ *   topk       1..nsrc: C_j = mean of the topk smallest per-source costs (ascending, summed left to right, / (float)topk)
+ *   var_min    > 0: a source is invalid where var_r < var_min or var_w < var_min, or any window sample is invalid
+ *   cost_max   depth = 0 where C_{j*} >= cost_max
+ *   moments    row sums of 2r+1 terms left to right, then the row sums top to bottom: S_r, S_rr, S_w, S_ww, S_rw
+ *   cost_s     1 - cov / sqrtf(var_r*var_w) clamped to [0, 2] with var = S_xx - (S_x*S_x)/n, cov = S_rw - (S_r*S_w)/n;
+ *              2 for an invalid source, and for every source where the reference window leaves the frame
+ *   j*         the first j of smallest C_j; if 0 < j* < ndepth-1, den = (C_{j*-1} + C_{j*+1}) - 2*C_{j*} and
+ *              delta = den > 0 ? clamp(0.5*(C_{j*-1} - C_{j*+1})/den, -0.5, 0.5) : 0,
+ *              invd* = invd[j*] + delta*(delta >= 0 ? invd[j*+1]-invd[j*] : invd[j*]-invd[j*-1]); else invd* = invd[j*]
+ *   depth_dev  [h][w] float32 1/invd*, 0 where the reference window leaves the frame or C_{j*} >= cost_max
+ *   cost_dev   [h][w] float32 C_{j*}
+ *   plane_dev  optional [h][w] int32 j* (NULL: not written)
+ *   volume_dev optional [ndepth][h][w] float32 C_j (NULL: not written; the volume never reaches HBM otherwise)
+ * Whether the optional outputs are present changes no other output.  No workspace.
+ *
+ * sfm_mvs_consistency — geometric-consistency filter of one reference depth map and the world point of each kept pixel.
+ *   depth_dev      [h][w] float32 reference depth map (0 = no depth)
+ *   nbr_depth_dev  host array of nview DEVICE pointers to the neighbours' [h][w] depth maps, 0 <= nview <= 8
+ *   nbr_index_host host int32 [nview] the neighbours' view indices; ref_index the reference's
+ *   ab_host        host float32 [nview][12] = A (3x3) | b (3): p_i = d*((A_i0*x + A_i1*y) + A_i2) + b_i; neighbour v is consistent
+ *                  iff p_2 > 0, its nearest pixel (floor(p_0/p_2 + 0.5), floor(p_1/p_2 + 0.5)) lies in the frame, the neighbour's
+ *                  depth dv there is > 0 and |p_2 - dv| <= tau*dv
+ *   bc_host        host float32 [12] = B (3x3) | c (3): xyz_i = d*((B_i0*x + B_i1*y) + B_i2) + c_i
+ *   tau >= 0 (finite), 0 <= min_consistent <= nview, 1 <= w, h <= 32767
+ *   unique         != 0: a pixel with a consistent neighbour of lower view index is dropped (the lowest-index consistent observer
+ *                  emits a surface sample, once)
+ *   mask_dev       [h][w] uint8 1 = kept (d > 0, count >= min_consistent, unique rule), else 0
+ *   xyz_dev        [h][w][3] float32 world point, 0 where the mask is 0
+ * Compaction: sfm_mask_indices over the masks.  No workspace.
+ * ---------------------------------------------------------------------- */
+int sfm_mvs_plane_sweep(const uint8_t* ref_dev, const uint8_t* const* src_dev, const float* mv_host, int nsrc, int64_t w, int64_t h,
+                        const float* invd_dev, int ndepth, int radius, int topk, float var_min, float cost_max,
+                        float* depth_dev, float* cost_dev, int32_t* plane_dev, float* volume_dev, void* stream);
+int sfm_mvs_consistency(const float* depth_dev, const float* const* nbr_depth_dev, const int32_t* nbr_index_host,
+                        const float* ab_host, int nview, int ref_index, const float* bc_host, int64_t w, int64_t h, float tau,
+                        int min_consistent, int unique, uint8_t* mask_dev, float* xyz_dev, void* stream);
 
 /* ------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets

@@ -1,0 +1,237 @@
+"""Plane-sweep multi-view stereo: the dense half of sfm-mvs (sfm.py:298 `densify = False`; the dense.ply branch of to_ply,
+sfm.py:194-201, that the reference never feeds).
+
+Thin, validating wrappers over `sfm_mvs_plane_sweep` and `sfm_mvs_consistency` (include/sfm_hip.h): device tensors in, device
+tensors out, stream ordered, no CPU path.  The host part is the geometry of a handful of 3x3 matrices per view (float64, cast
+once to float32) and the choice of the depth range from the sparse cloud.  docs/mvs.md describes the algorithm and its numbers.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import SfmHipError, check, on_device, ptr, require_cuda, stream_ptr
+
+MAX_VIEWS = 8       # sources per sweep, neighbours per consistency check
+
+
+def _rt(K, P):
+    """[R|t] = K^-1 P (float64)."""
+    Rt = np.linalg.solve(np.asarray(K, np.float64), np.asarray(P, np.float64).reshape(3, 4))
+    return Rt[:, :3], Rt[:, 3]
+
+
+def _inverse_depths_host(dmin, dmax, ndepth):
+    dmin, dmax, ndepth = float(dmin), float(dmax), int(ndepth)
+    if not (0.0 < dmin < dmax < np.inf) or ndepth < 2:
+        raise SfmHipError(f"inverse_depths: need 0 < dmin < dmax and ndepth >= 2 (got {dmin}, {dmax}, {ndepth})")
+    return np.linspace(1.0 / dmax, 1.0 / dmin, ndepth, dtype=np.float64).astype(np.float32)
+
+
+def _upload(a, device):
+    """Host array -> device tensor without a host wait: staged in pinned memory, copied on the current stream (the pinned block
+    is kept until that copy has run).  A pageable upload would synchronise the stream."""
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
+
+
+def inverse_depths(dmin, dmax, ndepth, device=None):
+    """`ndepth` plane inverse depths uniform between 1/dmax and 1/dmin (ascending: far to near), computed in float64 and returned
+    as a float32 device tensor (stream-ordered upload, no host wait)."""
+    return _upload(_inverse_depths_host(dmin, dmax, ndepth), device if device is not None else torch.device("cuda"))
+
+
+def _camera_depths(X, P):
+    # P = K [R|t] with K's last row (0, 0, 1): P's third row is [R|t]'s, the camera depth of X
+    P = np.asarray(P, np.float64).reshape(3, 4)
+    return X @ P[2, :3] + P[2, 3]
+
+
+def depth_range(Xtot, P_ref, lo=2, hi=98, P_all=None):
+    """(dmin, dmax) of the plane sweep of the camera P_ref: the lo / hi percentiles of the sparse points' camera depths, widened
+    by x0.8 and x1.25.  Monocular SfM fixes no scale, so the range has to come from the cloud.  With fewer than 8 points in front
+    of P_ref, the depths of the points in front of every camera of P_all (when given) are pooled instead."""
+    X = np.asarray(Xtot, np.float64).reshape(-1, 3)
+    z = _camera_depths(X, P_ref)
+    z = z[z > 0]
+    if len(z) < 8 and P_all is not None:
+        z = np.concatenate([_camera_depths(X, P) for P in np.asarray(P_all, np.float64).reshape(-1, 3, 4)])
+        z = z[z > 0]
+    if len(z) < 8:
+        raise SfmHipError(f"depth_range: only {len(z)} sparse points lie in front of the camera(s)")
+    a, b = np.percentile(z, [lo, hi])
+    return 0.8 * float(a), 1.25 * float(b)
+
+
+def neighbours(i, n, nsrc=4):
+    """The `nsrc` views nearest to view i in sequence order (i-1, i+1, i-2, i+2, ...), clipped to 0..n-1: the reference's
+    frames follow a camera path.  Near the ends of the sequence the list continues on the one side that is left."""
+    out = []
+    for d in range(1, n):
+        for v in (i - d, i + d):
+            if 0 <= v < n and len(out) < nsrc:
+                out.append(v)
+    return out
+
+
+def _relative(K, P_ref, P_other):
+    """(G, g): the pixel of the reference at depth d maps to d*(G x~) + g in the other camera (homogeneous, its z the camera
+    depth there): G = K R_o R_r^T K^-1, g = K (t_o - R_o R_r^T t_r)."""
+    K = np.asarray(K, np.float64)
+    Rr, tr = _rt(K, P_ref)
+    Ro, to = _rt(K, P_other)
+    Rrel = Ro @ Rr.T
+    return K @ Rrel @ np.linalg.inv(K), K @ (to - Rrel @ tr)
+
+
+def sweep_matrices(K, P_ref, P_srcs):
+    """float32 [nsrc, 12] = M_s (3x3 row-major) | v_s per source: a reference pixel on the plane of inverse depth q maps to
+    M_s x~ + v_s q (homogeneous) in source s."""
+    out = np.empty((len(P_srcs), 12), np.float64)
+    for s, P in enumerate(P_srcs):
+        M, v = _relative(K, P_ref, P)
+        out[s, :9], out[s, 9:] = M.ravel(), v
+    return out.astype(np.float32)
+
+
+def consistency_matrices(K, P_ref, P_nbrs):
+    """(ab float32 [nview, 12] = A_v | b_v per neighbour — the same formula as sweep_matrices —, bc float32 [12] = B | c with
+    B = R_r^T K^-1, c = -R_r^T t_r: the world point of reference pixel x~ at depth d is d*(B x~) + c)."""
+    K = np.asarray(K, np.float64)
+    ab = sweep_matrices(K, P_ref, P_nbrs).reshape(-1, 12)
+    Rr, tr = _rt(K, P_ref)
+    bc = np.concatenate([(Rr.T @ np.linalg.inv(K)).ravel(), -Rr.T @ tr])
+    return ab, bc.astype(np.float32)
+
+
+def _gray(t):
+    if t.dtype != torch.uint8 or t.dim() != 2:
+        raise SfmHipError("mvs: gray frames must be (H, W) uint8 device tensors")
+    return t.contiguous()
+
+
+def plane_sweep(ref, srcs, mv, invd, radius=3, topk=2, var_min=None, cost_max=None, plane=False, volume=False):
+    """Depth map of the gray reference frame `ref` against the gray `srcs` (sfm_mvs_plane_sweep).
+    ref, srcs: (H, W) uint8 device tensors; mv: float32 [nsrc, 12] (sweep_matrices); invd: float32 [ndepth] device tensor.
+    Returns (depth, cost, plane or None, volume or None): [H, W] float32, [H, W] float32, [H, W] int32, [ndepth, H, W] float32."""
+    var_min = VAR_MIN if var_min is None else var_min
+    cost_max = COST_MAX if cost_max is None else cost_max
+    require_cuda(ref, invd, *srcs)
+    ref = _gray(ref)
+    srcs = [_gray(s) for s in srcs]
+    h, w = ref.shape
+    if any(s.shape != ref.shape or s.device != ref.device for s in srcs):
+        raise SfmHipError("plane_sweep: every source frame must have the reference's size and device")
+    if invd.dtype != torch.float32 or invd.dim() != 1 or invd.device != ref.device:
+        raise SfmHipError("plane_sweep: invd must be a float32 vector on the reference's device")
+    invd = invd.contiguous()
+    mv = np.ascontiguousarray(np.asarray(mv, np.float32).reshape(-1, 12))
+    if len(mv) != len(srcs):
+        raise SfmHipError(f"plane_sweep: {len(srcs)} sources but {len(mv)} matrices")
+    nd = invd.numel()
+    dev = ref.device
+    depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+    cost = torch.empty((h, w), dtype=torch.float32, device=dev)
+    pl = torch.empty((h, w), dtype=torch.int32, device=dev) if plane else None
+    vol = torch.empty((nd, h, w), dtype=torch.float32, device=dev) if volume else None
+    src_ptrs = (ctypes.c_void_p * max(len(srcs), 1))(*[s.data_ptr() for s in srcs])
+    with on_device(dev):
+        check(_lib.lib().sfm_mvs_plane_sweep(ptr(ref), src_ptrs, mv.ctypes.data_as(ctypes.c_void_p), len(srcs), w, h, ptr(invd), nd,
+                                             int(radius), int(topk), float(var_min), float(cost_max), ptr(depth), ptr(cost), ptr(pl),
+                                             ptr(vol), stream_ptr()), "sfm_mvs_plane_sweep")
+    return depth, cost, pl, vol
+
+
+def consistency(depth, nbr_depths, nbr_index, ab, ref_index, bc, tau=0.01, min_consistent=2, unique=True, mask_out=None, xyz_out=None):
+    """Geometric-consistency mask of a reference depth map and the world point of each kept pixel (sfm_mvs_consistency).
+    depth, nbr_depths: [H, W] float32 device tensors; nbr_index: the neighbours' view indices; ab, bc: consistency_matrices.
+    mask_out / xyz_out: optional contiguous [H, W] uint8 / [H, W, 3] float32 outputs (e.g. one view's slice of a stacked buffer).
+    Returns (mask, xyz)."""
+    require_cuda(depth, *nbr_depths)
+    if depth.dtype != torch.float32 or depth.dim() != 2 or any(d.shape != depth.shape or d.dtype != torch.float32 for d in nbr_depths):
+        raise SfmHipError("consistency: depth maps must be [H, W] float32 of one size")
+    depth = depth.contiguous()
+    nbr_depths = [d.contiguous() for d in nbr_depths]
+    h, w = depth.shape
+    dev = depth.device
+    ab = np.ascontiguousarray(np.asarray(ab, np.float32).reshape(-1, 12))
+    bc = np.ascontiguousarray(np.asarray(bc, np.float32).reshape(12))
+    idx = np.ascontiguousarray(np.asarray(nbr_index, np.int32).reshape(-1))
+    if len(ab) != len(nbr_depths) or len(idx) != len(nbr_depths):
+        raise SfmHipError("consistency: one matrix and one view index per neighbour depth map")
+    mask = torch.empty((h, w), dtype=torch.uint8, device=dev) if mask_out is None else mask_out
+    xyz = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if xyz_out is None else xyz_out
+    if mask.shape != (h, w) or mask.dtype != torch.uint8 or not mask.is_contiguous() or xyz.shape != (h, w, 3) \
+            or xyz.dtype != torch.float32 or not xyz.is_contiguous():
+        raise SfmHipError("consistency: mask_out / xyz_out must be contiguous [H, W] uint8 / [H, W, 3] float32")
+    dptrs = (ctypes.c_void_p * max(len(nbr_depths), 1))(*[d.data_ptr() for d in nbr_depths])
+    with on_device(dev):
+        check(_lib.lib().sfm_mvs_consistency(ptr(depth), dptrs, idx.ctypes.data_as(ctypes.c_void_p), ab.ctypes.data_as(ctypes.c_void_p),
+                                             len(nbr_depths), int(ref_index), bc.ctypes.data_as(ctypes.c_void_p), w, h, float(tau),
+                                             int(min_consistent), 1 if unique else 0, ptr(mask), ptr(xyz), stream_ptr()),
+              "sfm_mvs_consistency")
+    return mask, xyz
+
+
+# Defaults of run_mvs, chosen on the CPU model (tests/np_mvs.py) over the rendered scenes of tests/mvs_scenes.py
+# (tests/test_mvs_cpu.py::test_algorithm_accuracy_on_a_rendered_scene; docs/mvs.md, "Calibration").
+VAR_MIN = 200.0     # sum of squared deviations over the window: a (2r+1)^2 = 49-pixel window with a gray-level std of ~2
+COST_MAX = 0.3      # aggregated 1 - ZNCC (top 2 of 4 sources) above which a pixel gets no depth
+
+
+def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_min=VAR_MIN, cost_max=COST_MAX, tau=0.01,
+            min_consistent=2, unique=True):
+    """Dense reconstruction of a registered sequence: a plane-sweep depth map per view, geometric-consistency filtering, and one
+    coloured cloud.
+
+    images:  BGR uint8 frames at K's resolution (the halved frames sfm.py:40 works on), device tensors or host arrays, in the
+             order of posearr's cameras
+    posearr: sfm.py:423's layout, K (9) then one 3x4 P per camera (pipeline.run_sfm's "posearr"); Xtot the sparse cloud
+    Per view: planes uniform in inverse depth over depth_range(Xtot, P_i), the `nsrc` sequence neighbours as sources (the same
+    views check its consistency), a pixel kept when >= `min_consistent` neighbours see its depth within `tau` relative, once
+    (unique: by its lowest-index consistent observer).
+    Defaults (VAR_MIN, COST_MAX, ndepth 128, r 3, 4 sources, top 2, tau 1 %, 2 consistent neighbours): docs/mvs.md, "Calibration".
+    Returns dict(depths [per view (H, W) float32 device tensor], points (m, 3) float64, colors (m, 3) float64 B G R): shaped as
+    Xtot / colorstot, so that pipeline.to_ply(path, points, colors, densify=True) writes Point_Cloud/dense.ply.
+    One host wait per call: the fused point count (then one download of the points and colours); every upload is stream-ordered
+    (pinned memory)."""
+    from . import ops
+    from .sift import bgr2gray
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    Ps = np.asarray(posearr, np.float64)[9:].reshape(-1, 3, 4)
+    n = len(Ps)
+    if len(images) != n:
+        raise SfmHipError(f"run_mvs: {len(images)} frames for {n} cameras")
+    if n < 2:
+        raise SfmHipError("run_mvs: needs at least two registered views")
+    nsrc = min(int(nsrc), n - 1, MAX_VIEWS)
+    topk = min(int(topk), nsrc)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if all(torch.is_tensor(im) and im.is_cuda for im in images):
+        frames = [im.to(dev).contiguous() for im in images]
+    else:                                                       # host frames: one pinned upload for all of them
+        host = [im.cpu().numpy() if torch.is_tensor(im) else np.asarray(im) for im in images]
+        if any(im.shape != host[0].shape or im.dtype != np.uint8 for im in host):
+            raise SfmHipError("run_mvs: frames must be (H, W, 3) uint8 BGR of one size")
+        frames = list(_upload(np.stack(host), dev))
+    if any(f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.shape != frames[0].shape for f in frames):
+        raise SfmHipError("run_mvs: frames must be (H, W, 3) uint8 BGR of one size")
+    h, w = frames[0].shape[:2]
+    grays = [bgr2gray(f) for f in frames]
+    nbrs = [neighbours(i, n, nsrc) for i in range(n)]
+    # every view's planes in one upload, before the first launch (a per-view upload would wait for the previous view's sweep)
+    invd = _upload(np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)]), dev)
+    depths = []
+    for i in range(n):
+        mv = sweep_matrices(K, Ps[i], Ps[nbrs[i]])
+        d, _, _, _ = plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, topk, var_min, cost_max)
+        depths.append(d)
+    masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    for i in range(n):
+        ab, bc = consistency_matrices(K, Ps[i], Ps[nbrs[i]])
+        consistency(depths[i], [depths[v] for v in nbrs[i]], nbrs[i], ab, i, bc, tau, min(int(min_consistent), len(nbrs[i])), unique,
+                    mask_out=masks[i], xyz_out=xyz[i])
+    idx = ops.mask_indices(masks).long()                       # the one host wait: the count sizes the result
+    both = torch.cat([xyz.reshape(-1, 3)[idx].double(), torch.stack(frames).reshape(-1, 3)[idx].double()], 1).cpu().numpy()
+    return dict(depths=depths, points=np.ascontiguousarray(both[:, :3]), colors=np.ascontiguousarray(both[:, 3:]))

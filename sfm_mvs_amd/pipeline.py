@@ -306,10 +306,24 @@ class FeatureStream:
                 self._cv.notify_all()
 
 
-def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=False, gtol_thresh=0.5, profile=None):
+def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=False, gtol_thresh=0.5, profile=None, densify=False,
+                   mvs_options=None):
     """sfm.py's main loop from pixels: img_downscale (:40), cvtColor + SIFT (:243-252) and the driver (:274-423).
     `images`: BGR uint8 frames in sequence order; K is scaled by the caller as in sfm.py:20-26.
-    profile: a DriverProfile — the run is then a PROFILED one (the device is drained at every stage boundary)."""
+    profile: a DriverProfile — the run is then a PROFILED one (the device is drained at every stage boundary).
+    densify: sfm.py:298's global — True runs the plane-sweep MVS (mvs.run_mvs, keyword arguments `mvs_options`) on the halved
+    frames already in HBM after the chain and sets out["dense"] (points / colors for to_ply(..., densify=True)); False changes
+    nothing."""
+    out = _run_sfm_images(images, K, downscale, log, be, bundle_adjustment, gtol_thresh, profile)
+    if densify:
+        from . import mvs
+        out["dense"] = mvs.run_mvs(out.pop("_small"), K, out["posearr"], out["Xtot"], **(mvs_options or {}))
+    else:
+        out.pop("_small")
+    return out
+
+
+def _run_sfm_images(images, K, downscale, log, be, bundle_adjustment, gtol_thresh, profile):
     import time
     if be is None and profile is None:
         # the product path: features are produced AHEAD of the sequential driver by a second host thread (FeatureStream)
@@ -323,6 +337,7 @@ def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=
                 out = run_sfm(feats, K, images=feats.small, log=log, bundle_adjustment=bundle_adjustment, gtol_thresh=gtol_thresh)
             cur.wait_stream(hp)
             out["features"] = list(feats)
+            out["_small"] = feats.small
         finally:
             feats.close()
         return out
@@ -355,6 +370,7 @@ def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=
         torch.cuda.synchronize()
         profile.wall = time.perf_counter() - t_all
     out["features"] = feats
+    out["_small"] = small
     return out
 
 
