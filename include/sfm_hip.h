@@ -30,7 +30,8 @@ extern "C" {
 #endif
 
 #define SFM_ABI_VERSION 3   /* 3 (round 6): + sfm_host_poll_count, sfm_debug_pnp_sweep_server; sfm_build_id() names every source file;
-                               later, backward-compatible additions: sfm_mvs_plane_sweep, sfm_mvs_consistency */
+                               later, backward-compatible additions: sfm_mvs_plane_sweep, sfm_mvs_consistency; sfm_tsdf_integrate,
+                               sfm_mesh_count(_ws_bytes), sfm_mesh_extract(_ws_bytes) */
 
 #define SFM_OK             0
 #define SFM_ERR_ARG       -1   /* null pointer, negative size, unsupported dim, misaligned pointer/stride */
@@ -574,6 +575,70 @@ int sfm_mvs_plane_sweep(const uint8_t* ref_dev, const uint8_t* const* src_dev, c
 int sfm_mvs_consistency(const float* depth_dev, const float* const* nbr_depth_dev, const int32_t* nbr_index_host,
                         const float* ab_host, int nview, int ref_index, const float* bc_host, int64_t w, int64_t h, float tau,
                         int min_consistent, int unique, uint8_t* mask_dev, float* xyz_dev, void* stream);
+
+/* ------------------------------------------------------------------------
+ * MESH  a surface from the MVS depth maps     after sfm.py:298 (`densify`)
+ *
+ * Volumetric fusion of depth maps into a truncated signed distance field (TSDF) and its zero set by marching tetrahedra
+ * (sfm_mvs_amd/mesh.py, docs/mesh.md).  As in "MVS", every step is a correctly rounded float32 operation in the order written
+ * here (no FMA, no reassociation), so an independent float32 restatement reproduces the outputs bit for bit.
+ *
+ * Grid: nx, ny, nz >= 2 lattice points per axis, nx*ny*nz <= 2^27; point (i, j, k) has linear index (k*ny + j)*nx + i and sits
+ * at x = ox + (float)i*voxel, y = oy + (float)j*voxel, z = oz + (float)k*voxel (origin_host float32 [3] = ox, oy, oz; voxel > 0).
+ *
+ * sfm_tsdf_integrate — folds nview views into the running sums of every lattice point.  No workspace, no atomics.
+ *   depth_dev  [nview][h][w] float32 camera depth, 0 = no depth; 1 <= w, h <= 32767, nview >= 0
+ *   mask_dev   optional [nview][h][w] uint8: a pixel is used only where it is nonzero (NULL: every pixel)
+ *   bgr_dev    optional [nview][h][w][3] uint8 B, G, R (NULL: no colour; then CWc_dev must be NULL too)
+ *   P_dev      [nview][12] float32 = K[R|t] row-major (formed in float64 by the caller, cast once)
+ *   trunc      > 0 (finite)
+ *   per view v in ascending order:  p_r = ((P_r0*x + P_r1*y) + P_r2*z) + P_r3;  the sample is valid iff p_2 > 0, the nearest
+ *              pixel (u, t) = (floor(p_0/p_2 + 0.5), floor(p_1/p_2 + 0.5)) lies in the frame (0 <= u <= w-1, 0 <= t <= h-1 tested
+ *              in float), d = depth[v][t][u] > 0 and the mask there (if given) is nonzero;  sdf = d - p_2;  no contribution if
+ *              sdf < -trunc;  otherwise f = min(sdf, trunc) / trunc, S = S + f, W = W + 1, and where also sdf <= trunc:
+ *              C_b = C_b + (float)B, C_g = C_g + (float)G, C_r = C_r + (float)R, Wc = Wc + 1
+ *   S_dev, W_dev  [nz][ny][nx] float32, read and written back once per call (the caller zeroes them before the first call)
+ *   CWc_dev    optional [nz][ny][nx][4] float32 (C_b, C_g, C_r, Wc), likewise
+ *   Sums run left to right in view order from the values read, so integrating views in two consecutive calls is bit-identical
+ *   to one call over all of them.
+ *
+ * sfm_mesh_count / sfm_mesh_extract — marching tetrahedra over a finished field.
+ *   w_min      >= 1 (finite): point p is known iff W >= w_min; its value F = S/W, it is inside iff F < 0
+ *   cube (i, j, k), i < nx-1, j < ny-1, k < nz-1, is split into the 6 Kuhn tetrahedra {000, e1, e1+e2, 111}, the permutations
+ *              (e1, e2, e3) in the order xyz, xzy, yxz, yzx, zxy, zyx; corners are numbered 0..3 in that order; a tetrahedron with
+ *              an unknown corner emits nothing
+ *   edges      every tetrahedron edge joins a lattice point a to a + one of the 7 directions, numbered 0..6: +x, +y, +z, +x+y, +x+z,
+ *              +y+z, +x+y+z; it belongs to a (its lower end).  Edge (a, dir) with b = a + dir in the grid crosses iff a and b are
+ *              both known and exactly one of them is inside.
+ *   vertices   one per crossing edge; its id is the exclusive count of crossing edges before it in (linear index of a, dir) order.
+ *              t = Fa / (Fa - Fb); position xa + t*(xb - xa) per coordinate (xa, xb by the lattice formula above); colour
+ *              ca + t*(cb - ca) per channel (B, G, R), c = C/Wc per channel, or 0 where Wc = 0
+ *   triangles  per tetrahedron with every corner known: one inside or one outside corner c -> 1 triangle over the 3 crossing
+ *              edges (c, o) in ascending order of the other corner o; two of each -> 2 triangles splitting the quad on the diagonal
+ *              from edge (in0, out0) to edge (in1, out1) (in0 < in1, out0 < out1 in corner order): (in0,out0) (in0,out1) (in1,out1)
+ *              and (in0,out0) (in1,out1) (in1,out0).  A triangle whose right-hand normal would point from outside to inside has
+ *              its last two vertices swapped.  Order: cube linear index, tetrahedron, triangle.
+ *   The case table is generated from these rules at compile time (csrc/mesh.hip); consistent splitting across neighbouring
+ *   cubes makes the surface watertight wherever the field is known.  Counts are int32: 7*2^27 edges and 12*2^27 triangles fit.
+ *
+ *   sfm_mesh_count     counts_dev int32[2] = (vertices, triangles), written on the stream (the caller reads them to size the
+ *                      outputs).  Workspace: sfm_mesh_count_ws_bytes.
+ *   sfm_mesh_extract   vertices_dev [max_vertices][3] float32, optional colors_dev [max_vertices][3] float32 B G R (needs CWc_dev),
+ *                      faces_dev [max_faces][3] int32 vertex ids.  Writes exactly the counted elements; nothing past max_vertices /
+ *                      max_faces is written (the caller passes the counts).  Workspace: sfm_mesh_extract_ws_bytes (5 bytes per
+ *                      lattice point and a little).  Deterministic: two passes with an int32 scan, no atomics.
+ * The _ws_bytes twins return 0 for an invalid grid.
+ * ---------------------------------------------------------------------- */
+int sfm_tsdf_integrate(const float* depth_dev, const uint8_t* mask_dev, const uint8_t* bgr_dev, const float* P_dev, int nview, int64_t w,
+                       int64_t h, const float* origin_host, float voxel, int64_t nx, int64_t ny, int64_t nz, float trunc, float* S_dev,
+                       float* W_dev, float* CWc_dev, void* stream);
+size_t sfm_mesh_count_ws_bytes(int64_t nx, int64_t ny, int64_t nz);
+int sfm_mesh_count(const float* S_dev, const float* W_dev, int64_t nx, int64_t ny, int64_t nz, float w_min, int32_t* counts_dev,
+                   void* ws_dev, size_t ws_bytes, void* stream);
+size_t sfm_mesh_extract_ws_bytes(int64_t nx, int64_t ny, int64_t nz);
+int sfm_mesh_extract(const float* S_dev, const float* W_dev, const float* CWc_dev, const float* origin_host, float voxel, int64_t nx,
+                     int64_t ny, int64_t nz, float w_min, int64_t max_vertices, int64_t max_faces, float* vertices_dev, float* colors_dev,
+                     int32_t* faces_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets

@@ -1,0 +1,197 @@
+"""A surface from the MVS depth maps: TSDF fusion and a watertight mesh by marching tetrahedra (the step sfm-mvs tools take after
+the dense cloud; the reference's `camera_orientation` writes triangle meshes with open3d).
+
+Thin, validating wrappers over `sfm_tsdf_integrate`, `sfm_mesh_count` and `sfm_mesh_extract` (include/sfm_hip.h, "MESH"): device
+tensors in, device tensors out, stream ordered, no CPU path.  The host part is the choice of the volume from the fused cloud
+(float64) and the cast of the cameras' projection matrices.  docs/mesh.md describes the algorithm and its numbers.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import SfmHipError, check, on_device, ptr, require_cuda, stream_ptr
+from .mvs import _upload
+
+MAX_POINTS = 1 << 27            # lattice points per grid
+
+# Defaults of run_mesh, chosen on the CPU model (tests/np_mesh.py) over the rendered scenes of tests/mvs_scenes.py
+# (docs/mesh.md, "Calibration").
+TRUNC_VOXELS = 2.0              # truncation distance in voxels
+W_MIN = 3.0                     # observations a lattice point needs to be known
+
+
+def volume_bounds(points, resolution=256, pad=0.05):
+    """The grid of a fused cloud: per axis the 1st / 99th percentiles of `points` ((m, 3), host float64), widened by `pad` times
+    the longest extent on each side; voxel = longest padded extent / (resolution - 1).
+    Returns (origin float64 (3,), voxel float, dims (nx, ny, nz)) with max(dims) == resolution.  Raises SfmHipError on a cloud
+    with fewer than 4 finite points or no extent, and when the grid would exceed 2^27 lattice points."""
+    X = np.asarray(points, np.float64).reshape(-1, 3)
+    X = X[np.all(np.isfinite(X), axis=1)]
+    resolution = int(resolution)
+    if resolution < 2:
+        raise SfmHipError(f"volume_bounds: resolution {resolution} < 2")
+    if not (0.0 <= pad < np.inf):
+        raise SfmHipError(f"volume_bounds: pad {pad} must be finite and >= 0")
+    if len(X) < 4:
+        raise SfmHipError(f"volume_bounds: {len(X)} finite points: too few for a volume")
+    lo, hi = np.percentile(X, 1, axis=0), np.percentile(X, 99, axis=0)
+    ext = hi - lo
+    longest = float(ext.max())
+    if not longest > 0.0:
+        raise SfmHipError("volume_bounds: the cloud has no extent (all points coincide)")
+    lo, hi = lo - pad * longest, hi + pad * longest
+    ext = hi - lo
+    voxel = float(ext.max()) / (resolution - 1)
+    dims = tuple(int(max(2, min(resolution, int(np.ceil(e / voxel - 1e-9)) + 1))) for e in ext)
+    if int(np.prod(dims, dtype=np.int64)) > MAX_POINTS:
+        raise SfmHipError(f"volume_bounds: {dims[0]} x {dims[1]} x {dims[2]} grid exceeds 2^27 lattice points; lower the resolution")
+    return lo, voxel, dims
+
+
+def projection_rows(K, Ps):
+    """float32 [n, 12] = K[R|t] row-major per camera: sfm.py:423's posearr stores P = K[R|t] itself (formed in float64, cast once)."""
+    return np.ascontiguousarray(np.asarray(Ps, np.float64).reshape(-1, 12)).astype(np.float32)
+
+
+def _origin(origin):
+    return np.ascontiguousarray(np.asarray(origin, np.float64).reshape(3).astype(np.float32))
+
+
+def tsdf_integrate(depths, P, origin, voxel, dims, trunc, masks=None, bgr=None, S=None, W=None, C=None):
+    """Fold views into the TSDF sums (sfm_tsdf_integrate).
+    depths [n, H, W] float32 device tensor; P float32 [n, 12] (host array: uploaded through pinned memory; or a device tensor);
+    masks optional [n, H, W] uint8; bgr optional [n, H, W, 3] uint8; origin (3,), voxel, dims (nx, ny, nz), trunc (world units).
+    S, W [nz, ny, nx] float32 and C [nz, ny, nx, 4] float32 continue earlier sums (zeros when None; the colour sums C are kept
+    exactly when bgr is given).  Returns (S, W, C or None), updated in place when given."""
+    require_cuda(depths, masks, bgr, S, W, C)
+    nx, ny, nz = (int(d) for d in dims)
+    if depths.dtype != torch.float32 or depths.dim() != 3:
+        raise SfmHipError("tsdf_integrate: depths must be an [n, H, W] float32 device tensor")
+    depths = depths.contiguous()
+    n, h, w = depths.shape
+    dev = depths.device
+    if masks is not None and (masks.dtype != torch.uint8 or tuple(masks.shape) != (n, h, w)):
+        raise SfmHipError("tsdf_integrate: masks must be [n, H, W] uint8 like the depths")
+    if bgr is not None and (bgr.dtype != torch.uint8 or tuple(bgr.shape) != (n, h, w, 3)):
+        raise SfmHipError("tsdf_integrate: bgr must be [n, H, W, 3] uint8 like the depths")
+    if torch.is_tensor(P):
+        require_cuda(P)
+        Pd = P.to(dev, torch.float32).contiguous().reshape(-1, 12)
+    else:
+        Pd = _upload(np.ascontiguousarray(np.asarray(P, np.float32).reshape(-1, 12)), dev)
+    if Pd.shape[0] != n:
+        raise SfmHipError(f"tsdf_integrate: {n} depth maps but {Pd.shape[0]} projection matrices")
+    if S is None:
+        S = torch.zeros((nz, ny, nx), dtype=torch.float32, device=dev)
+    if W is None:
+        W = torch.zeros((nz, ny, nx), dtype=torch.float32, device=dev)
+    if C is None and bgr is not None:
+        C = torch.zeros((nz, ny, nx, 4), dtype=torch.float32, device=dev)
+    for t, shape in ((S, (nz, ny, nx)), (W, (nz, ny, nx))) + (((C, (nz, ny, nx, 4)),) if C is not None else ()):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise SfmHipError(f"tsdf_integrate: sums must be contiguous float32 {shape} on the depths' device")
+    if (C is None) != (bgr is None):
+        raise SfmHipError("tsdf_integrate: colour sums C go with bgr")
+    org = _origin(origin)
+    with on_device(dev):
+        check(_lib.lib().sfm_tsdf_integrate(ptr(depths), ptr(None if masks is None else masks.contiguous()),
+                                            ptr(None if C is None else bgr.contiguous()), ptr(Pd), n, w, h, org.ctypes.data, float(voxel),
+                                            nx, ny, nz, float(trunc), ptr(S), ptr(W), ptr(C), stream_ptr()), "sfm_tsdf_integrate")
+    return S, W, C
+
+
+def _field(S, W, C):
+    require_cuda(S, W, C)
+    if S.dtype != torch.float32 or W.dtype != torch.float32 or S.dim() != 3 or S.shape != W.shape:
+        raise SfmHipError("mesh: S and W must be [nz, ny, nx] float32 device tensors of one shape")
+    nz, ny, nx = S.shape
+    if C is not None and (C.dtype != torch.float32 or tuple(C.shape) != (nz, ny, nx, 4)):
+        raise SfmHipError("mesh: C must be [nz, ny, nx, 4] float32")
+    return S.contiguous(), W.contiguous(), None if C is None else C.contiguous(), (nx, ny, nz)
+
+
+def mesh_counts(S, W, w_min=W_MIN):
+    """sfm_mesh_count: an int32 [2] device tensor (vertices, triangles); no host wait."""
+    from .ops import _workspace
+    S, W, _, (nx, ny, nz) = _field(S, W, None)
+    L = _lib.lib()
+    out = torch.empty(2, dtype=torch.int32, device=S.device)
+    ws = _workspace(S.device, L.sfm_mesh_count_ws_bytes(nx, ny, nz))
+    with on_device(S.device):
+        check(L.sfm_mesh_count(ptr(S), ptr(W), nx, ny, nz, float(w_min), ptr(out), ptr(ws), ws.numel(), stream_ptr()), "sfm_mesh_count")
+    return out
+
+
+def extract_mesh(S, W, C, origin, voxel, w_min=W_MIN, packed=False):
+    """Marching tetrahedra over the field (sfm_mesh_count, one host read of the two totals, sfm_mesh_extract).
+    Returns device tensors (vertices [m, 3] float32, colors [m, 3] float32 B G R or None (C None), faces [k, 3] int32).
+    packed=True: also the one int32 buffer all three live in, so that a caller downloads them with a single copy."""
+    from .ops import _workspace
+    S, W, C, (nx, ny, nz) = _field(S, W, C)
+    nv, nt = (int(v) for v in mesh_counts(S, W, w_min).cpu())        # the host wait: the totals size the outputs
+    dev = S.device
+    ncol = nv if C is not None else 0
+    buf = torch.empty(3 * nv + 3 * ncol + 3 * nt, dtype=torch.int32, device=dev)
+    verts = buf[:3 * nv].view(torch.float32).view(nv, 3)
+    cols = buf[3 * nv:3 * (nv + ncol)].view(torch.float32).view(ncol, 3) if C is not None else None
+    faces = buf[3 * (nv + ncol):].view(nt, 3)
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_mesh_extract_ws_bytes(nx, ny, nz))
+    org = _origin(origin)
+    with on_device(dev):
+        check(L.sfm_mesh_extract(ptr(S), ptr(W), ptr(C), org.ctypes.data, float(voxel), nx, ny, nz, float(w_min), nv, nt,
+                                 ptr(verts) if nv else None, ptr(cols) if ncol else None, ptr(faces) if nt else None, ptr(ws), ws.numel(),
+                                 stream_ptr()), "sfm_mesh_extract")
+    return (verts, cols, faces, buf) if packed else (verts, cols, faces)
+
+
+def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOXELS, w_min=W_MIN, tau=0.01, min_consistent=2, nsrc=4,
+             pad=0.05):
+    """A coloured triangle mesh of a registered sequence from run_mvs's depth maps.
+
+    images:  the BGR uint8 frames run_mvs got (device tensors or host arrays, K's resolution, posearr's camera order)
+    mvs_out: run_mvs's result: its per-view depth maps and its fused cloud (which fixes the volume: volume_bounds)
+    Per view a consistency mask (mvs.consistency with unique=False: every pixel >= `min_consistent` of its `nsrc` sequence
+    neighbours agree with, within `tau`), then one sfm_tsdf_integrate over all views (truncation `trunc_voxels` voxels),
+    marching tetrahedra over the points seen `w_min` times.  Defaults: docs/mesh.md, "Calibration".
+    Returns dict(vertices (m, 3) float64, colors (m, 3) float64 B G R, faces (k, 3) int32) for pipeline.to_ply_mesh.
+    Two host waits per call: the mesh totals and the one download; every upload is stream-ordered (pinned memory)."""
+    from . import mvs
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    Ps = np.asarray(posearr, np.float64)[9:].reshape(-1, 3, 4)
+    n = len(Ps)
+    depths = list(mvs_out["depths"])
+    if len(images) != n or len(depths) != n:
+        raise SfmHipError(f"run_mesh: {len(images)} frames and {len(depths)} depth maps for {n} cameras")
+    if n < 2:
+        raise SfmHipError("run_mesh: needs at least two registered views")
+    origin, voxel, dims = volume_bounds(mvs_out["points"], resolution, pad)
+    dev = depths[0].device
+    require_cuda(*depths)
+    if all(torch.is_tensor(im) and im.is_cuda for im in images):
+        frames = torch.stack([im.to(dev) for im in images]).contiguous()
+    else:
+        host = [im.cpu().numpy() if torch.is_tensor(im) else np.asarray(im) for im in images]
+        if any(im.shape != host[0].shape or im.dtype != np.uint8 for im in host):
+            raise SfmHipError("run_mesh: frames must be (H, W, 3) uint8 BGR of one size")
+        frames = _upload(np.stack(host), dev)
+    h, w = depths[0].shape
+    if frames.dim() != 4 or tuple(frames.shape[1:]) != (h, w, 3) or frames.dtype != torch.uint8:
+        raise SfmHipError("run_mesh: frames must be (H, W, 3) uint8 BGR at the depth maps' size")
+    nsrc = min(int(nsrc), n - 1, mvs.MAX_VIEWS)
+    masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for i in range(n):
+            nb = mvs.neighbours(i, n, nsrc)
+            ab, bc = mvs.consistency_matrices(K, Ps[i], Ps[nb])
+            mvs.consistency(depths[i], [depths[v] for v in nb], nb, ab, i, bc, tau, min(int(min_consistent), len(nb)), False,
+                            mask_out=masks[i], xyz_out=xyz[i])
+        S, W, C = tsdf_integrate(torch.stack(depths), projection_rows(K, Ps), origin, voxel, dims, float(trunc_voxels) * voxel,
+                                 masks=masks, bgr=frames)
+        verts, cols, faces, buf = extract_mesh(S, W, C, origin, voxel, w_min, packed=True)
+        host = buf.cpu().numpy()                                    # the one download
+    nv, nt = len(verts), len(faces)
+    fl = host[:6 * nv].view(np.float32)
+    return dict(vertices=fl[:3 * nv].reshape(nv, 3).astype(np.float64), colors=fl[3 * nv:].reshape(nv, 3).astype(np.float64),
+                faces=np.ascontiguousarray(host[6 * nv:].reshape(nt, 3)))

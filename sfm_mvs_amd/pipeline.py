@@ -307,17 +307,25 @@ class FeatureStream:
 
 
 def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=False, gtol_thresh=0.5, profile=None, densify=False,
-                   mvs_options=None):
+                   mvs_options=None, mesh=False, mesh_options=None):
     """sfm.py's main loop from pixels: img_downscale (:40), cvtColor + SIFT (:243-252) and the driver (:274-423).
     `images`: BGR uint8 frames in sequence order; K is scaled by the caller as in sfm.py:20-26.
     profile: a DriverProfile — the run is then a PROFILED one (the device is drained at every stage boundary).
     densify: sfm.py:298's global — True runs the plane-sweep MVS (mvs.run_mvs, keyword arguments `mvs_options`) on the halved
     frames already in HBM after the chain and sets out["dense"] (points / colors for to_ply(..., densify=True)); False changes
-    nothing."""
+    nothing.
+    mesh: True (needs densify) also fuses the depth maps into a surface (mesh.run_mesh on the same halved frames, keyword
+    arguments `mesh_options`) and sets out["mesh"] (vertices / colors / faces for to_ply_mesh)."""
+    if mesh and not densify:
+        raise ValueError("run_sfm_images: mesh=True needs densify=True (the mesh is fused from the MVS depth maps)")
     out = _run_sfm_images(images, K, downscale, log, be, bundle_adjustment, gtol_thresh, profile)
     if densify:
         from . import mvs
-        out["dense"] = mvs.run_mvs(out.pop("_small"), K, out["posearr"], out["Xtot"], **(mvs_options or {}))
+        small = out.pop("_small")
+        out["dense"] = mvs.run_mvs(small, K, out["posearr"], out["Xtot"], **(mvs_options or {}))
+        if mesh:
+            from . import mesh as mesh_mod
+            out["mesh"] = mesh_mod.run_mesh(small, K, out["posearr"], out["dense"], **(mesh_options or {}))
     else:
         out.pop("_small")
     return out
@@ -624,6 +632,30 @@ def to_ply(path, point_cloud, colors, densify=False):
         f.write("ply\n" + "".join("\t\t" + ln + "\n" for ln in lines) + "\t\t")
         np.savetxt(f, verts, "%f %f %f %d %d %d")
     return len(verts)
+
+
+def to_ply_mesh(path, vertices, colors, faces):
+    """Point_Cloud/dense_mesh.ply: the surface of mesh.run_mesh in to_ply's units and columns (x200, B G R uchar, so that it
+    overlays sparse.ply and dense.ply), colours rounded as floor(c + 0.5) clamped to 0..255, plus `element face k` with
+    `property list uchar int vertex_indices`.  No centroid outlier cut: it would leave faces pointing at dropped vertices.
+    Returns (vertices, faces) written."""
+    verts = np.asarray(vertices, np.float64).reshape(-1, 3) * 200
+    cols = np.clip(np.floor(np.asarray(colors, np.float64).reshape(-1, 3) + 0.5), 0, 255).astype(np.int64)
+    tris = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    if len(cols) != len(verts):
+        raise ValueError(f"to_ply_mesh: {len(verts)} vertices but {len(cols)} colours")
+    if len(tris) and (tris.min() < 0 or tris.max() >= len(verts)):
+        raise ValueError("to_ply_mesh: a face names a vertex that does not exist")
+    lines = ["ply", "format ascii 1.0", "element vertex %d" % len(verts), "property float x", "property float y", "property float z",
+             "property uchar blue", "property uchar green", "property uchar red", "element face %d" % len(tris),
+             "property list uchar int vertex_indices", "end_header"]
+    with open(path + "/Point_Cloud/dense_mesh.ply", "w") as f:
+        f.write("\n".join(lines) + "\n")
+        if len(verts):
+            np.savetxt(f, np.hstack([verts, cols]), "%f %f %f %d %d %d")
+        if len(tris):
+            np.savetxt(f, np.hstack([np.full((len(tris), 1), 3), tris]), "%d %d %d %d")
+    return len(verts), len(tris)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
