@@ -529,6 +529,11 @@ int sfm_sift_detect_and_compute(const uint8_t* gray_dev, int64_t w, int64_t h, i
  * (sfm_mvs_amd/mvs.py, docs/mvs.md).  Every step is a correctly rounded
  * float32 operation in the order written here (no FMA, no reassociation), so
  * an independent float32 restatement reproduces the outputs bit for bit.
+ * Non-finite inputs (matrix entries, depths, field values) follow IEEE 754
+ * through the same operations: a comparison with a NaN is false, so a NaN
+ * depth is no depth and a NaN h_2 or p_2 no sample.  Where an output is a NaN,
+ * its sign and payload are unspecified (IEEE 754 leaves them to the
+ * implementation); the same holds for "MESH" below.
  *
  * sfm_mvs_plane_sweep — the depth map of one reference view.
  *   ref_dev    [h][w] uint8 reference gray frame; I' = (float)I - 128

@@ -393,14 +393,17 @@ FUZZ_SOURCES = {
     "sift": ("sift.hip", "common.h"),
     "geometry": ("ransac.hip", "residual.hip", "triangulate.hip", "assoc.hip", "ba_dense.hip", "ba_schur.hip", "blocks.hip", "host_solvers.h", "common.h"),
     "pipeline": ("knn.hip", "sift.hip", "ransac.hip", "residual.hip", "triangulate.hip", "assoc.hip", "blocks.hip", "host_solvers.h", "common.h"),
+    "mvs": ("mvs.hip", "common.h"),
+    "mesh": ("mesh.hip", "common.h"),
 }
-FUZZ_MIN_CASES = {"knn": 20000, "sift": 500, "geometry": 2000, "pipeline": 200}
+FUZZ_MIN_CASES = {"knn": 20000, "sift": 500, "geometry": 2000, "pipeline": 200,
+                  "mvs": 100, "mesh": 800}      # about a tenth of the logged totals (1 116 and 8 319: docs/mvs.md, docs/mesh.md), as for the other four
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("family", sorted(FUZZ_SOURCES))
 def test_committed_fuzz_logs_are_those_of_the_loaded_binary(family):
-    """The long randomised parity sweeps (scripts/fuzz_knn.py, fuzz_sift.py, fuzz_geometry.py, fuzz_pipeline.py) are committed under
+    """The long randomised parity sweeps (scripts/fuzz_knn.py, fuzz_sift.py, fuzz_geometry.py, fuzz_pipeline.py, fuzz_mvs.py, fuzz_mesh.py) are committed under
     profiles/ with the build id of the library they ran on: the code hash of EVERY source file (comments and whitespace removed,
     scripts/knn_code_hash.py: a documentation-only edit keeps them valid).  Each family is checked against the hashes of ITS sources
     in the id of the LOADED library (sfm_build_id(): baked in at build time — round 5 stamped everything with knn.hip's hash alone, so

@@ -13,6 +13,7 @@ if HERE not in sys.path:
 
 import np_mvs  # noqa: E402
 from mvs_scenes import gray, render_scene, scene_cloud, surface_error  # noqa: E402
+from parity_cases import np_run_mvs  # noqa: E402
 
 
 def bits(t):
@@ -117,28 +118,6 @@ def test_full_size_depth_map_is_bit_identical(hip):
     d, c, pl, _ = mvs.plane_sweep(up(grays[2]), [up(grays[v]) for v in nb], mv, invd, 3, 2, mvs.VAR_MIN, mvs.COST_MAX, plane=True)
     wd, wc, wpl, _ = np_mvs.plane_sweep(grays[2], [grays[v] for v in nb], mv, invd.cpu().numpy(), 3, 2, mvs.VAR_MIN, mvs.COST_MAX)
     assert same(d, wd) and same(c, wc) and same(pl, wpl)
-
-
-def np_run_mvs(grays, bgrs, K, posearr, Xtot, ndepth, radius, nsrc, topk, var_min, cost_max, tau, min_consistent, unique):
-    """run_mvs restated with np_mvs, fed the product's float32 matrices and plane inverse depths (what the kernels got)."""
-    from sfm_mvs_amd import mvs
-    Ps = np.asarray(posearr)[9:].reshape(-1, 3, 4)
-    n = len(Ps)
-    nbrs = [mvs.neighbours(i, n, nsrc) for i in range(n)]
-    depths = []
-    for i in range(n):
-        dmin, dmax = mvs.depth_range(Xtot, Ps[i], P_all=Ps)
-        invd = mvs.inverse_depths(dmin, dmax, ndepth).cpu().numpy()
-        depths.append(np_mvs.plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mvs.sweep_matrices(K, Ps[i], Ps[nbrs[i]]), invd, radius,
-                                         topk, var_min, cost_max)[0])
-    masks, xyzs = [], []
-    for i in range(n):
-        ab, bc = mvs.consistency_matrices(K, Ps[i], Ps[nbrs[i]])
-        m, x = np_mvs.consistency(depths[i], [depths[v] for v in nbrs[i]], nbrs[i], ab, i, bc, tau, min_consistent, unique)
-        masks.append(m)
-        xyzs.append(x)
-    idx = np.flatnonzero(np.stack(masks).reshape(-1))
-    return depths, np.stack(xyzs).reshape(-1, 3)[idx].astype(np.float64), np.stack(bgrs).reshape(-1, 3)[idx].astype(np.float64)
 
 
 @pytest.mark.gpu

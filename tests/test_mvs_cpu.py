@@ -185,3 +185,92 @@ def test_fused_cloud_lies_on_the_rendered_surfaces():
     pts = np.stack(xyzs).reshape(-1, 3)[np.flatnonzero(np.stack(masks).reshape(-1))].astype(np.float64)
     assert len(pts) > 5000
     assert float((surface_error(pts, K, P, gt) <= 0.01).mean()) >= MIN_FUSED_WITHIN_1PCT
+
+
+def _window_total(a, r):
+    """Sum over the (2r+1)^2 window about every interior pixel, float64, explicit loops over the window's offsets."""
+    h, w = a.shape
+    out = np.zeros((h - 2 * r, w - 2 * r), np.float64)
+    for dy in range(2 * r + 1):
+        for dx in range(2 * r + 1):
+            out += a[dy:dy + h - 2 * r, dx:dx + w - 2 * r]
+    return out
+
+
+def zncc_cost_f64_with_bound(R, W, valid, r, var_min):
+    """1 - ZNCC of the float32 frames R (reference I') and W (warped source, as given) in float64, two passes (means, then the
+    moments of the deviations), and the first-order bound of what the float32 one-pass route of the header may differ by.
+    -> (c64 clamped to [0, 2], ok64, bound on |c32 - c64|, near: var within its bound of var_min), all [h - 2r, w - 2r].
+
+    float32 route: each of the five sums S_r, S_rr, S_w, S_ww, S_rw adds (2r+1)^2 terms, row sums left to right and the row sums
+    top to bottom, so that any term passes k = 4r additions: |error| <= k u sum|x_i| with u = 2^-24 (recursive summation), and
+    one more u for the rounded products.  var = S_xx - (S_x*S_x)/n rounds three times more, cov likewise; the quotient
+    cov / sqrt(var_r*var_w) takes the relative errors of its parts to first order."""
+    u = 2.0 ** -24
+    k = 4 * r
+    n = float((2 * r + 1) ** 2)
+    R, W = R.astype(np.float64), W.astype(np.float64)
+    h, w = R.shape
+    ih, iw = h - 2 * r, w - 2 * r
+    m_r, m_w = _window_total(R, r) / n, _window_total(W, r) / n
+    var_r, var_w, cov = (np.zeros((ih, iw)) for _ in range(3))
+    for dy in range(2 * r + 1):
+        for dx in range(2 * r + 1):
+            a, b = R[dy:dy + ih, dx:dx + iw] - m_r, W[dy:dy + ih, dx:dx + iw] - m_w
+            var_r += a * a
+            var_w += b * b
+            cov += a * b
+    bad = _window_total((~valid).astype(np.float64), r) > 0
+    # errors of the float32 sums
+    e_r, e_w = k * u * _window_total(np.abs(R), r), k * u * _window_total(np.abs(W), r)
+    e_rr, e_ww, e_rw = ((k + 1) * u * _window_total(np.abs(x), r) for x in (R * R, W * W, R * W))
+    s_r, s_w = n * m_r, n * m_w
+    e_var_r = e_rr + 2 * np.abs(s_r) * e_r / n + 2 * u * s_r * s_r / n + u * np.abs(var_r)
+    e_var_w = e_ww + 2 * np.abs(s_w) * e_w / n + 2 * u * s_w * s_w / n + u * np.abs(var_w)
+    e_cov = e_rw + (np.abs(s_r) * e_w + np.abs(s_w) * e_r) / n + 2 * u * np.abs(s_r * s_w) / n + u * np.abs(cov)
+    near = (np.abs(var_r - var_min) <= e_var_r) | (np.abs(var_w - var_min) <= e_var_w)
+    ok = ~bad & ~(var_r < var_min) & ~(var_w < var_min)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        root = np.sqrt(np.where(ok, var_r * var_w, 1.0))
+        q = cov / root
+        rel_root = 0.5 * (e_var_r / np.where(ok, var_r, 1.0) + e_var_w / np.where(ok, var_w, 1.0) + u) + u
+        e_q = e_cov / root + np.abs(q) * (rel_root + u)
+        c = 1.0 - q
+    bound = e_q + u * np.abs(c)
+    return np.where(ok, np.clip(c, 0.0, 2.0), 2.0), ok, bound, near & ~bad
+
+
+MAX_LEFT_OUT = 0.01                # of the interior pixel-plane pairs: variance within its error bound of var_min
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+@pytest.mark.parametrize("radius", [1, 3])
+def test_one_pass_float32_moments_stay_within_their_error_bound_of_float64(seed, radius):
+    """The checker's own delicate step: np_mvs.plane_sweep's per-source cost (one source, topk 1, the volume) against a float64
+    two-pass ZNCC over the SAME float32 warped frame, per pixel and plane within the propagated rounding bound; validity agrees
+    exactly outside the band where the float64 variance lies within its bound of var_min (at most 1 % of the pairs)."""
+    import np_mvs
+    from mvs_scenes import gray, render_scene
+    from sfm_mvs_amd import mvs
+    var_min = 150.0
+    imgs, K, P, _ = render_scene(n=5, w=160, h=120, seed=seed)
+    grays = [gray(im) for im in imgs]
+    invd = np.linspace(1.0 / 9.0, 1.0 / 1.5, 12).astype(np.float32)
+    R = grays[2].astype(np.float32) - np.float32(128)
+    worst, left_out, pairs = 0.0, 0, 0
+    for v in mvs.neighbours(2, 5, 4):
+        mv = mvs.sweep_matrices(K, P[2], P[[v]])
+        c32 = np_mvs.plane_sweep(grays[2], [grays[v]], mv, invd, radius, 1, var_min, 2.5)[3][:, radius:-radius, radius:-radius]
+        for j in range(len(invd)):
+            W, valid = np_mvs.warp(grays[v], mv[0], invd[j], 160, 120)
+            c64, ok, bound, near = zncc_cost_f64_with_bound(R, W, valid, radius, var_min)
+            keep = ~near
+            assert np.all(c32[j][keep & ~ok] == 2.0)
+            sel = keep & ok
+            ratio = np.abs(c32[j][sel].astype(np.float64) - c64[sel]) / bound[sel]
+            worst = max(worst, float(ratio.max()) if ratio.size else 0.0)
+            left_out += int(near.sum())
+            pairs += near.size
+    print(f"seed {seed} r {radius}: largest |c32 - c64| / bound {worst:.3f}, left out {left_out} of {pairs} pairs ({100.0 * left_out / pairs:.4f} %)")
+    assert worst <= 1.0, worst
+    assert left_out <= MAX_LEFT_OUT * pairs, (left_out, pairs)
