@@ -31,7 +31,8 @@ extern "C" {
 
 #define SFM_ABI_VERSION 3   /* 3 (round 6): + sfm_host_poll_count, sfm_debug_pnp_sweep_server; sfm_build_id() names every source file;
                                later, backward-compatible additions: sfm_mvs_plane_sweep, sfm_mvs_consistency; sfm_tsdf_integrate,
-                               sfm_mesh_count(_ws_bytes), sfm_mesh_extract(_ws_bytes) */
+                               sfm_mesh_count(_ws_bytes), sfm_mesh_extract(_ws_bytes); sfm_mvs_cost_shift, sfm_mvs_cost_aggregate,
+                               sfm_mvs_cost_depth */
 
 #define SFM_OK             0
 #define SFM_ERR_ARG       -1   /* null pointer, negative size, unsupported dim, misaligned pointer/stride */
@@ -582,7 +583,53 @@ int sfm_mvs_consistency(const float* depth_dev, const float* const* nbr_depth_de
                         int min_consistent, int unique, uint8_t* mask_dev, float* xyz_dev, void* stream);
 
 /* ------------------------------------------------------------------------
- * MESH  a surface from the MVS depth maps     after sfm.py:298 (`densify`)
+ * MVS-AGGREGATE  shiftable windows and semi-global aggregation of the sweep's cost volume (opt-in; no reference counterpart)
+ *
+ * Three entry points between sfm_mvs_plane_sweep (volume_dev) and sfm_mvs_consistency (sfm_mvs_amd/mvs.py `aggregate_depth`,
+ * docs/mvs.md §7).  Only the quantisation and the final parabola touch floating point; everything between is integer
+ * arithmetic, hence exact and independent of any summation order, so an integer restatement (tests/np_mvs_aggregate.py)
+ * reproduces every output bit for bit.  Volumes are plane-major [ndepth][h][w], element (j, y, x) at (j*h + y)*w + x (64-bit).
+ * Limits of all three, as the sweep's: 2 <= ndepth <= 1024, 1 <= w, h <= 32767.  No workspace, no atomics on global memory,
+ * no host wait.
+ *
+ * sfm_mvs_cost_shift — quantise and take the best window that contains the pixel (a spatial min filter per plane).
+ *   volume_dev [ndepth][h][w] float32 costs (the sweep's C_j in [0, 2]; any float is accepted)
+ *   q(c)       = !(c < 2) ? 2048 : (c > 0 ? (uint16)floorf(c*1024.f + 0.5f) : 0), the product and the sum correctly rounded
+ *                float32 operations: both comparisons are false for a NaN, so a NaN gives 2048; +inf gives 2048, every
+ *                c <= 0 (-0, negatives, -inf) gives 0.  q is monotone and 0 <= q <= 2048.
+ *   shift      0..4;  q_dev [ndepth][h][w] uint16:  Q(j, y, x) = min of q(volume(j, y+dy, x+dx)) over |dx|, |dy| <= shift with
+ *              0 <= x+dx <= w-1 and 0 <= y+dy <= h-1 (the taps outside the frame are left out; shift 0 is q alone).
+ *              Because q is monotone, filtering before or after quantising is the same function.
+ *
+ * sfm_mvs_cost_aggregate — Hirschmueller's path costs summed over ndir directions.
+ *   q_dev, s_dev  [ndepth][h][w] uint16, distinct buffers;  integers 0 <= p1 <= p2 <= 2048;  ndir 4 or 8: the first ndir of
+ *              (dx, dy) = (1,0), (-1,0), (0,1), (0,-1), (1,1), (-1,1), (1,-1), (-1,-1)
+ *   L_r        for direction r = (dx, dy) the predecessor of p = (x, y) is p' = (x-dx, y-dy).  p' outside the frame:
+ *              L_r(p, j) = Q(p, j).  Otherwise, with m = min_k L_r(p', k):
+ *              L_r(p, j) = Q(p, j) + min(L_r(p', j), L_r(p', j-1) + p1, L_r(p', j+1) + p1, m + p2) - m
+ *              (the j-1 term is absent for j = 0, the j+1 term for j = ndepth-1).
+ *   S(p, j)    = sum over the ndir directions of L_r(p, j).
+ *   Ranges: the min is >= m and <= m + p2, so Q <= L_r <= Q + p2 <= 2048 + 2048 = 4096, and S <= 8*4096 = 32768: uint16
+ *   holds every value.  (A caller's own Q above 2048 is accepted: L_r is formed in 32 bits and S is the sum modulo 65536.)
+ *
+ * sfm_mvs_cost_depth — winner-take-all on S with the sweep's sub-plane parabola.
+ *   j*         the first j of smallest S(p, j).  If 0 < j* < ndepth-1: a = (float)S(j*-1), b = (float)S(j*), c = (float)S(j*+1)
+ *              (exact), den = (a + c) - 2*b, delta = den > 0 ? clamp(0.5*(a - c)/den, -0.5, 0.5) : 0,
+ *              invd* = invd[j*] + delta*(delta >= 0 ? invd[j*+1]-invd[j*] : invd[j*]-invd[j*-1]); else invd* = invd[j*]
+ *              (float32, each operation correctly rounded in the order written, no FMA — as sfm_mvs_plane_sweep)
+ *   gate       integer 0..65535 (the wrapper passes q(cost_max))
+ *   depth_dev  [h][w] float32 1/invd*, 0 where Q(p, j*) >= gate
+ *   cost_dev   [h][w] float32 (float)Q(p, j*) / 1024
+ *   plane_dev  optional [h][w] int32 j* (NULL: not written; changes no other output)
+ * ---------------------------------------------------------------------- */
+int sfm_mvs_cost_shift(const float* volume_dev, int64_t w, int64_t h, int ndepth, int shift, uint16_t* q_dev, void* stream);
+int sfm_mvs_cost_aggregate(const uint16_t* q_dev, int64_t w, int64_t h, int ndepth, int p1, int p2, int ndir, uint16_t* s_dev,
+                           void* stream);
+int sfm_mvs_cost_depth(const uint16_t* s_dev, const uint16_t* q_dev, const float* invd_dev, int64_t w, int64_t h, int ndepth, int gate,
+                       float* depth_dev, float* cost_dev, int32_t* plane_dev, void* stream);
+
+/* ------------------------------------------------------------------------
+ * MESH a surface from the MVS depth maps     after sfm.py:298 (`densify`)
  *
  * Volumetric fusion of depth maps into a truncated signed distance field (TSDF) and its zero set by marching tetrahedra
  * (sfm_mvs_amd/mesh.py, docs/mesh.md).  As in "MVS", every step is a correctly rounded float32 operation in the order written

@@ -110,9 +110,10 @@ def _gray(t):
     return t.contiguous()
 
 
-def plane_sweep(ref, srcs, mv, invd, radius=3, topk=2, var_min=None, cost_max=None, plane=False, volume=False):
+def plane_sweep(ref, srcs, mv, invd, radius=3, topk=2, var_min=None, cost_max=None, plane=False, volume=False, volume_out=None):
     """Depth map of the gray reference frame `ref` against the gray `srcs` (sfm_mvs_plane_sweep).
     ref, srcs: (H, W) uint8 device tensors; mv: float32 [nsrc, 12] (sweep_matrices); invd: float32 [ndepth] device tensor.
+    volume_out: an optional contiguous [ndepth, H, W] float32 device tensor the volume is written to (implies volume=True).
     Returns (depth, cost, plane or None, volume or None): [H, W] float32, [H, W] float32, [H, W] int32, [ndepth, H, W] float32."""
     var_min = VAR_MIN if var_min is None else var_min
     cost_max = COST_MAX if cost_max is None else cost_max
@@ -133,7 +134,9 @@ def plane_sweep(ref, srcs, mv, invd, radius=3, topk=2, var_min=None, cost_max=No
     depth = torch.empty((h, w), dtype=torch.float32, device=dev)
     cost = torch.empty((h, w), dtype=torch.float32, device=dev)
     pl = torch.empty((h, w), dtype=torch.int32, device=dev) if plane else None
-    vol = torch.empty((nd, h, w), dtype=torch.float32, device=dev) if volume else None
+    vol = volume_out if volume_out is not None else torch.empty((nd, h, w), dtype=torch.float32, device=dev) if volume else None
+    if vol is not None and (vol.shape != (nd, h, w) or vol.dtype != torch.float32 or vol.device != dev or not vol.is_contiguous()):
+        raise SfmHipError("plane_sweep: volume_out must be a contiguous [ndepth, H, W] float32 tensor on the reference's device")
     src_ptrs = (ctypes.c_void_p * max(len(srcs), 1))(*[s.data_ptr() for s in srcs])
     with on_device(dev):
         check(_lib.lib().sfm_mvs_plane_sweep(ptr(ref), src_ptrs, mv.ctypes.data_as(ctypes.c_void_p), len(srcs), w, h, ptr(invd), nd,
@@ -173,14 +176,98 @@ def consistency(depth, nbr_depths, nbr_index, ab, ref_index, bc, tau=0.01, min_c
     return mask, xyz
 
 
+def _volume_u16(t, what):
+    if not torch.is_tensor(t) or t.dtype != torch.uint16 or t.dim() != 3:
+        raise SfmHipError(f"{what}: needs a [ndepth, H, W] uint16 device tensor")
+    require_cuda(t)
+    return t.contiguous()
+
+
+def _out_like(out, shape, dtype, dev, what):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise SfmHipError(f"{what}: out must be a contiguous {tuple(shape)} {dtype} tensor on the input's device")
+    return out
+
+
+def quantise_cost(c):
+    """q(c) of include/sfm_hip.h ("MVS-AGGREGATE") for one host float: the integer cost at 1/1024 (a NaN gives 2048)."""
+    c = np.float32(c)
+    if not c < np.float32(2):
+        return 2048
+    return int(np.floor(c * np.float32(1024) + np.float32(0.5))) if c > np.float32(0) else 0
+
+
+def cost_shift(volume, shift, out=None):
+    """Quantised, shiftable-window cost volume (sfm_mvs_cost_shift): float32 [ndepth, H, W] -> uint16 Q of the same shape, the
+    minimum of round(1024 c) over the (2 shift + 1)^2 taps in the frame; shift 0..4."""
+    require_cuda(volume)
+    if volume.dtype != torch.float32 or volume.dim() != 3:
+        raise SfmHipError("cost_shift: volume must be a [ndepth, H, W] float32 device tensor")
+    volume = volume.contiguous()
+    nd, h, w = volume.shape
+    q = _out_like(out, volume.shape, torch.uint16, volume.device, "cost_shift")
+    with on_device(volume.device):
+        check(_lib.lib().sfm_mvs_cost_shift(ptr(volume), w, h, nd, int(shift), ptr(q), stream_ptr()), "sfm_mvs_cost_shift")
+    return q
+
+
+def cost_aggregate(q, p1=None, p2=None, ndir=8, out=None):
+    """Semi-global path costs of Q summed over `ndir` (4 or 8) directions (sfm_mvs_cost_aggregate): uint16 [ndepth, H, W] -> uint16
+    S of the same shape; integer penalties 0 <= p1 <= p2 <= 2048 in units of 1/1024 (defaults P1, P2)."""
+    q = _volume_u16(q, "cost_aggregate")
+    nd, h, w = q.shape
+    s = _out_like(out, q.shape, torch.uint16, q.device, "cost_aggregate")
+    with on_device(q.device):
+        check(_lib.lib().sfm_mvs_cost_aggregate(ptr(q), w, h, nd, int(P1 if p1 is None else p1), int(P2 if p2 is None else p2), int(ndir),
+                                                ptr(s), stream_ptr()), "sfm_mvs_cost_aggregate")
+    return s
+
+
+def cost_depth(s, q, invd, gate, plane=True):
+    """Depth map of an aggregated volume (sfm_mvs_cost_depth): the first plane of smallest S, the sweep's parabola on S, no depth
+    where Q there is >= the integer `gate`.  Returns (depth [H, W] float32, cost [H, W] float32 = Q/1024, plane [H, W] int32 or
+    None)."""
+    s, q = _volume_u16(s, "cost_depth"), _volume_u16(q, "cost_depth")
+    require_cuda(invd)
+    nd, h, w = s.shape
+    if q.shape != s.shape or q.device != s.device:
+        raise SfmHipError("cost_depth: S and Q must have one shape and device")
+    if invd.dtype != torch.float32 or invd.dim() != 1 or invd.numel() != nd or invd.device != s.device:
+        raise SfmHipError("cost_depth: invd must be a float32 vector of ndepth entries on the volumes' device")
+    invd = invd.contiguous()
+    dev = s.device
+    depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+    cost = torch.empty((h, w), dtype=torch.float32, device=dev)
+    pl = torch.empty((h, w), dtype=torch.int32, device=dev) if plane else None
+    with on_device(dev):
+        check(_lib.lib().sfm_mvs_cost_depth(ptr(s), ptr(q), ptr(invd), w, h, nd, int(gate), ptr(depth), ptr(cost), ptr(pl), stream_ptr()),
+              "sfm_mvs_cost_depth")
+    return depth, cost, pl
+
+
+def aggregate_depth(volume, invd, shift=None, p1=None, p2=None, ndir=8, cost_max=None, q_out=None, s_out=None):
+    """The aggregated depth map of a sweep's cost volume: cost_shift, cost_aggregate, cost_depth with gate = q(cost_max).
+    q_out / s_out: optional uint16 buffers of the volume's shape to reuse.  Returns (depth, cost, plane)."""
+    q = cost_shift(volume, SHIFT if shift is None else shift, out=q_out)
+    s = cost_aggregate(q, p1, p2, ndir, out=s_out)
+    return cost_depth(s, q, invd, quantise_cost(COST_MAX if cost_max is None else cost_max))
+
+
 # Defaults of run_mvs, chosen on the CPU model (tests/np_mvs.py) over the rendered scenes of tests/mvs_scenes.py
 # (tests/test_mvs_cpu.py::test_algorithm_accuracy_on_a_rendered_scene; docs/mvs.md, "Calibration").
 VAR_MIN = 200.0     # sum of squared deviations over the window: a (2r+1)^2 = 49-pixel window with a gray-level std of ~2
 COST_MAX = 0.3      # aggregated 1 - ZNCC (top 2 of 4 sources) above which a pixel gets no depth
+# Defaults of the opt-in aggregation (run_mvs(aggregate=True)), chosen by the sweep of docs/mvs.md §7 over the same scenes
+# (tests/test_mvs_aggregate_cpu.py::test_calibration_on_the_rendered_scenes); penalties in units of 1/1024 of the cost
+SHIFT = 3           # half-width of the shiftable window's min filter (run_mvs: None = the sweep's radius)
+P1 = 10             # a change of one plane between neighbouring pixels
+P2 = 102            # any larger change
 
 
 def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_min=VAR_MIN, cost_max=COST_MAX, tau=0.01,
-            min_consistent=2, unique=True):
+            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8):
     """Dense reconstruction of a registered sequence: a plane-sweep depth map per view, geometric-consistency filtering, and one
     coloured cloud.
 
@@ -191,6 +278,9 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     views check its consistency), a pixel kept when >= `min_consistent` neighbours see its depth within `tau` relative, once
     (unique: by its lowest-index consistent observer).
     Defaults (VAR_MIN, COST_MAX, ndepth 128, r 3, 4 sources, top 2, tau 1 %, 2 consistent neighbours): docs/mvs.md, "Calibration".
+    aggregate: True replaces every view's winner-take-all depth map by aggregate_depth of the sweep's cost volume (shiftable
+             windows of half-width `shift`, None = radius; semi-global penalties p1 / p2 over `ndir` directions): docs/mvs.md §7.
+             The float volume, Q and S are allocated once and reused by every view (10 bytes per pixel and plane).
     Returns dict(depths [per view (H, W) float32 device tensor], points (m, 3) float64, colors (m, 3) float64 B G R): shaped as
     Xtot / colorstot, so that pipeline.to_ply(path, points, colors, densify=True) writes Point_Cloud/dense.ply.
     One host wait per call: the fused point count (then one download of the points and colours); every upload is stream-ordered
@@ -222,9 +312,17 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     # every view's planes in one upload, before the first launch (a per-view upload would wait for the previous view's sweep)
     invd = _upload(np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)]), dev)
     depths = []
+    if aggregate:
+        vol = torch.empty((int(ndepth), h, w), dtype=torch.float32, device=dev)
+        qbuf = torch.empty((int(ndepth), h, w), dtype=torch.uint16, device=dev)
+        sbuf = torch.empty((int(ndepth), h, w), dtype=torch.uint16, device=dev)
     for i in range(n):
         mv = sweep_matrices(K, Ps[i], Ps[nbrs[i]])
-        d, _, _, _ = plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, topk, var_min, cost_max)
+        if aggregate:
+            plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, topk, var_min, cost_max, volume_out=vol)
+            d, _, _ = aggregate_depth(vol, invd[i], radius if shift is None else shift, p1, p2, ndir, cost_max, q_out=qbuf, s_out=sbuf)
+        else:
+            d, _, _, _ = plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, topk, var_min, cost_max)
         depths.append(d)
     masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)

@@ -307,13 +307,15 @@ class FeatureStream:
 
 
 def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=False, gtol_thresh=0.5, profile=None, densify=False,
-                   mvs_options=None, mesh=False, mesh_options=None):
+                   mvs_options=None, mesh=False, mesh_options=None, aggregate=None):
     """sfm.py's main loop from pixels: img_downscale (:40), cvtColor + SIFT (:243-252) and the driver (:274-423).
     `images`: BGR uint8 frames in sequence order; K is scaled by the caller as in sfm.py:20-26.
     profile: a DriverProfile — the run is then a PROFILED one (the device is drained at every stage boundary).
     densify: sfm.py:298's global — True runs the plane-sweep MVS (mvs.run_mvs, keyword arguments `mvs_options`) on the halved
     frames already in HBM after the chain and sets out["dense"] (points / colors for to_ply(..., densify=True)); False changes
     nothing.
+    aggregate: with densify, True / False sets run_mvs's `aggregate` (shiftable windows + semi-global aggregation of every view's
+    cost volume, docs/mvs.md §7); None leaves it to `mvs_options`.
     mesh: True (needs densify) also fuses the depth maps into a surface (mesh.run_mesh on the same halved frames, keyword
     arguments `mesh_options`) and sets out["mesh"] (vertices / colors / faces for to_ply_mesh)."""
     if mesh and not densify:
@@ -322,7 +324,10 @@ def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=
     if densify:
         from . import mvs
         small = out.pop("_small")
-        out["dense"] = mvs.run_mvs(small, K, out["posearr"], out["Xtot"], **(mvs_options or {}))
+        opts = dict(mvs_options or {})
+        if aggregate is not None:
+            opts["aggregate"] = bool(aggregate)
+        out["dense"] = mvs.run_mvs(small, K, out["posearr"], out["Xtot"], **opts)
         if mesh:
             from . import mesh as mesh_mod
             out["mesh"] = mesh_mod.run_mesh(small, K, out["posearr"], out["dense"], **(mesh_options or {}))
