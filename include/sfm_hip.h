@@ -713,6 +713,9 @@ int sfm_debug_set_trace(void* dev_buf);
  * situation of a grid that is not co-resident (tests/test_gpu_knn_q8.py: the repair of pairs quantised in vain must not depend on
  * when a workgroup is dispatched).  workgroup = -1 switches it off. */
 int sfm_debug_knn_split_delay(int workgroup, int microseconds);
+/* Test hook: with on != 0 every following knn_prep_kernel launch sends pairs that are quantised for the integer body through the
+ * GENERAL row loop instead of the lean one (tests/test_gpu_knn_prep_lean.py: both must leave the same words).  0 switches it off. */
+int sfm_debug_knn_prep_general(int on);
 int sfm_profile_read(int slot, double* total_ms_host, int64_t* launches_host);
 /* How often library calls of this process have WAITED for the device so far (cumulative; the RANSAC entry points read the
  * hypothesis scores back chunk by chunk, the Schur solver its convergence scalars).  Diagnostics: bench.py reports the

@@ -808,13 +808,138 @@ __device__ __forceinline__ float fp16_chunk(const float (&in)[8], float sc, unsi
     return err2;
 }
 
+// Sum over the sixteen lanes of a row by DPP row rotations 8, 4, 2, 1.  After the step by m the value has period m within the
+// row, so lane + m (mod 16) holds what lane ^ m holds: the same pairs are added as by the xor butterfly (lane_xor<8> .. <1>),
+// with no trip through the LDS crossbar for the steps 8 and 4.
+template <typename V>
+__device__ __forceinline__ V row16_sum(V v) {
+    static_assert(sizeof(V) == 4, "one register");
+    auto rot = [](V x, auto ctrl) {
+        return __builtin_bit_cast(V, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + decltype(ctrl)::value /*row_ror*/, 0xF, 0xF, true));
+    };
+    v += rot(v, std::integral_constant<int, 8>{});
+    v += rot(v, std::integral_constant<int, 4>{});
+    v += rot(v, std::integral_constant<int, 2>{});
+    v += rot(v, std::integral_constant<int, 1>{});
+    return v;
+}
+
+// The row loop of knn_prep_kernel for ONE side (Q or T) of a pair that is being QUANTISED for the integer body in fragment
+// order (do8 && q8pair && frag): the same rows on the same lanes, the same expression trees and the same words as the
+// general loop leaves — byte image, integer norm, norm, residual, row mask, the train side's init fragment, the block
+// maxima — without what that loop carries for the other data kinds.  The side, the base pointers, the strides and the tile
+// offsets are wave-uniform (a wave's four rows never straddle a side or a 32-row tile) and live in scalar registers; a lane
+// forms its offsets once.  Independent subtracts / multiplies / FMAs go two to an instruction (packed fp32: the same IEEE
+// operations).  Padding rows write zero bytes, zero norms (train: +inf) and an empty row mask, as in the general loop; their
+// fp16 image is not written: nothing reads it while the pair stays quantised, and the repair (knn_split_images_kernel)
+// rewrites every row of the pair, padding included, when it does not.
+// Requires ld < 2^27 (32-bit lane offsets).
+template <bool kIsQ>
+__device__ __forceinline__ void prep_lean_rows(const float* __restrict__ src, int64_t ld, int n, int npad, int wrow /*the wave's first row (uniform)*/,
+                                               int rstep, const Q8Grid g8, unsigned char* __restrict__ img8, unsigned char* __restrict__ tfrag,
+                                               float* __restrict__ nrm_out, int* __restrict__ w_out, unsigned short* __restrict__ rm_out,
+                                               float* __restrict__ qerr, float& mx, float& mxe, float& mxq, unsigned& flags, int& w8min, int& w8max) {
+    constexpr int kAhead = 3;                                            // (kPrepAhead of the general loop)
+    constexpr int kTileB = kIsQ ? kI8QTileBytes : kI8TileBytes;
+    constexpr unsigned kFlip = kIsQ ? 0x7F7F7F7Fu : 0x80808080u;          // b = 127 - q,  a = t - 128
+    const unsigned c = threadIdx.x & 15, lr = (threadIdx.x >> 4) & 3;
+    const unsigned ldoff = ((unsigned)lr * (unsigned)ld + 8u * c) * 4u;
+    const unsigned imgoff = (c >> 2) * 1024 + ((c >> 1) & 1) * 512 + (lr << 4) + ((c & 1) << 3);
+    const unsigned fragoff = (c * 32 + lr) << 3;
+    const f32x2 lo2 = {g8.lo, g8.lo}, inv2 = {g8.inv, g8.inv}, s2 = {g8.s, g8.s};
+    unsigned sfl = 0;
+    for (int wb = wrow; wb < npad; wb += kAhead * rstep) {
+        float4 vin[kAhead][2];
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) {
+            const int wr = wb + k * rstep;
+            const char* p = reinterpret_cast<const char*>(src) + (int64_t)wr * ld * 4 + ldoff;
+            if (wr + 4 <= n) {                                           // (uniform: all four rows are real)
+                vin[k][0] = *reinterpret_cast<const float4*>(p);
+                vin[k][1] = *reinterpret_cast<const float4*>(p + 16);
+            } else {
+                vin[k][0] = vin[k][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if ((int)lr < n - wr) {                                  // (rows past npad are past n)
+                    vin[k][0] = *reinterpret_cast<const float4*>(p);
+                    vin[k][1] = *reinterpret_cast<const float4*>(p + 16);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) {
+            const int wr = wb + k * rstep;
+            if (wr >= npad) break;
+            const bool real = (int)lr < n - wr;
+            const f32x2 p0 = {vin[k][0].x, vin[k][0].y}, p1 = {vin[k][0].z, vin[k][0].w}, p2 = {vin[k][1].x, vin[k][1].y}, p3 = {vin[k][1].z, vin[k][1].w};
+            // ||row||^2: the balanced tree of the general loop
+            const f32x2 q0 = p0 * p0, q1 = p1 * p1, q2 = p2 * p2, q3 = p3 * p3;
+            const float s = row16_sum(((q0.x + q0.y) + (q1.x + q1.y)) + ((q2.x + q2.y) + (q3.x + q3.y)));
+            // k = the saturating, rounding conversion of (x - lo) * inv; residual x - fma(s, k, lo), one FMA chain in element order
+            const f32x2 u0 = (p0 - lo2) * inv2, u1 = (p1 - lo2) * inv2, u2 = (p2 - lo2) * inv2, u3 = (p3 - lo2) * inv2;
+            unsigned lo = __builtin_amdgcn_cvt_pk_u8_f32(u0.x, 0, 0u), hi = __builtin_amdgcn_cvt_pk_u8_f32(u2.x, 0, 0u);
+            lo = __builtin_amdgcn_cvt_pk_u8_f32(u0.y, 1, lo); hi = __builtin_amdgcn_cvt_pk_u8_f32(u2.y, 1, hi);
+            lo = __builtin_amdgcn_cvt_pk_u8_f32(u1.x, 2, lo); hi = __builtin_amdgcn_cvt_pk_u8_f32(u3.x, 2, hi);
+            lo = __builtin_amdgcn_cvt_pk_u8_f32(u1.y, 3, lo); hi = __builtin_amdgcn_cvt_pk_u8_f32(u3.y, 3, hi);
+            const f32x2 k0 = {(float)(lo & 0xFFu), (float)((lo >> 8) & 0xFFu)}, k1 = {(float)((lo >> 16) & 0xFFu), (float)(lo >> 24)};
+            const f32x2 k2 = {(float)(hi & 0xFFu), (float)((hi >> 8) & 0xFFu)}, k3 = {(float)((hi >> 16) & 0xFFu), (float)(hi >> 24)};
+            const f32x2 d0 = p0 - __builtin_elementwise_fma(s2, k0, lo2), d1 = p1 - __builtin_elementwise_fma(s2, k1, lo2);
+            const f32x2 d2 = p2 - __builtin_elementwise_fma(s2, k2, lo2), d3 = p3 - __builtin_elementwise_fma(s2, k3, lo2);
+            float e2 = fmaf(d0.x, d0.x, 0.f);
+            e2 = fmaf(d0.y, d0.y, e2); e2 = fmaf(d1.x, d1.x, e2); e2 = fmaf(d1.y, d1.y, e2);
+            e2 = fmaf(d2.x, d2.x, e2); e2 = fmaf(d2.y, d2.y, e2); e2 = fmaf(d3.x, d3.x, e2); e2 = fmaf(d3.y, d3.y, e2);
+            e2 = row16_sum(real ? e2 : 0.f);
+            const float err2 = e2 < kInf ? e2 : kInf;                    // (NaN / inf data: an infinite slack — everything is re-evaluated exactly)
+            if (wr < n) sfl = kFlagQ8;                                   // (some row of the wave is real)
+            if (wr < n && n - wr < 4) {
+                // the one wave of the side that holds real and padding rows: the general loop runs its 16-bit conversion there,
+                // and the real rows' exactness / range flags with it
+                float in[8] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
+                unsigned fw[4];
+                // (a real branch: the values pass through an empty asm so that the conversion is not speculated into the row loop)
+                asm volatile("; prep_lean_rows: mixed wave" : "+v"(in[0]), "+v"(in[1]), "+v"(in[2]), "+v"(in[3]), "+v"(in[4]), "+v"(in[5]), "+v"(in[6]), "+v"(in[7]));
+                (void)fp16_chunk(in, kIsQ ? -2.f : 1.f, fw, flags);
+            }
+            const float nrm = (kIsQ || real) ? s : kInf;                 // padded train rows can never be candidates
+            // (uniform offsets: the wave's tile and its four rows' place in it; 32-bit as everywhere for the fragment images)
+            const unsigned tile = (unsigned)wr >> 5, rin = (unsigned)wr & 31u;
+            if constexpr (!kIsQ) {
+                unsigned char* fbase = tfrag + (tile * (unsigned)kTileFragBytes + (8u * kFragBytes + (rin << 3)));
+                if (c < 2) *reinterpret_cast<uint2*>(fbase + fragoff) = frag_init_operand(nrm, false, c);
+            }
+            const unsigned long long m8 = __ballot(real);               // bit 16 k + c: chunk c of the wave's row k is in the byte image only
+            const unsigned x0 = real ? lo ^ kFlip : 0u, x1 = real ? hi ^ kFlip : 0u;   // rows past the end: zero bytes
+            int w8 = __builtin_amdgcn_sdot4((int)x0, (int)x0, 8, false);
+            w8 = __builtin_amdgcn_sdot4((int)x1, (int)x1, w8, false);
+            w8 = __builtin_amdgcn_sdot4((int)x0, 0x02020202, w8, false);
+            w8 = __builtin_amdgcn_sdot4((int)x1, 0x02020202, w8, false);
+            w8 = row16_sum(w8);
+            unsigned char* ibase = img8 + (tile * (unsigned)kTileB + (rin << 4));
+            *reinterpret_cast<uint2*>(ibase + imgoff) = make_uint2(x0, x1);
+            if (c == 0) {
+                (nrm_out + wr)[lr] = nrm;
+                (rm_out + wr)[lr] = (unsigned short)(m8 >> (threadIdx.x & 48));
+                (w_out + wr)[lr] = w8;
+                if constexpr (kIsQ) (qerr + wr)[lr] = err2;
+            }
+            if constexpr (kIsQ) {
+                mxq = fmaxf(mxq, s);
+            } else {
+                if (real) { w8min = min(w8min, w8); w8max = max(w8max, w8); }
+                mx = fmaxf(mx, s);
+                mxe = fmaxf(mxe, err2);
+            }
+        }
+    }
+    flags |= sfl;
+}
+
 // One pass over Q and T: rows → the fp16 image (Q pre-scaled by -2, exact), fp32 squared norms, per-block max of
 // ||t||^2 and exactness / range flags, zero the rescan counter.  Rows >= n of the padded images are zero-filled.
 // Image layout: [3][n_pad][128] 16-bit: bf16 hi, bf16 mid, fp16; the two bf16 planes are only needed by the split
 // arithmetic (values outside fp16's range) and are written by knn_split_images_kernel, which runs when the flags say so:
 // the common case moves 15 MB per 10k x 10k pair instead of 25.
 // Batched: grid = (blocks + 1, B); column b works on pair b (its workspace arrays sit at b * stride).
-constexpr int kPrepThreads = 256;      // one wave per SIMD, 56 registers: a prep workgroup of the NEXT launch set fits beside the q4 filter's waves
+constexpr int kPrepThreads = 256;      // one wave per SIMD, 103 registers (the general row loop's; docs/knn.md): a prep workgroup of the NEXT launch set fits beside the q4 filter's 380-register waves
 __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int64_t ldq, int nq, int nq_pad,
                                                        int64_t ldt, int nt, int nt_pad,
                                                        unsigned short* __restrict__ qsplit, float* __restrict__ qn,
@@ -837,7 +962,8 @@ __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int
                                                        unsigned short* __restrict__ rmt /*[s_tn]*/,
                                                        int64_t units8, int G8, int n_rb8, int64_t* __restrict__ wg_begin8,
                                                        int* __restrict__ rb_first8, int* __restrict__ rb_last8, int* __restrict__ wg_sbase8,
-                                                       int q8 /*1: float pairs are quantised for the integer body*/, int* __restrict__ minfo) {
+                                                       int q8 /*1: float pairs are quantised for the integer body*/, int* __restrict__ minfo,
+                                                       int prep_general /*test hook (sfm_debug_knn_prep_general): quantised pairs take the general row loop*/) {
     constexpr int kPrepWaves = kPrepThreads / 64, kPrepRows = kPrepThreads / 16;
     __shared__ float wmax[kPrepWaves];
     __shared__ float q8red[20];
@@ -892,6 +1018,14 @@ __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int
     // is worked on (the body is a dependent chain and a workgroup has only a few trips).
     constexpr int kPrepAhead = 3;
     const int row0 = blockIdx.x * kPrepRows + (threadIdx.x >> 4), rstep = nblk * kPrepRows;
+    if (do8 && q8pair && frag && !prep_general && ldq < (1 << 27) && ldt < (1 << 27)) {
+        // quantised pair (uniform over its workgroups): the lean loop, the Q rows and then the T rows, dealt as below
+        const int wq0 = blockIdx.x * kPrepRows + 4 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        int wt0 = wq0;
+        while (wt0 < nq_pad) wt0 += rstep;
+        prep_lean_rows<true>(Q, ldq, nq, nq_pad, wq0, rstep, g8, qi8, nullptr, qn, wq, rmq, qerr, mx, mxe, mxq, flags, w8min, w8max);
+        prep_lean_rows<false>(T, ldt, nt, nt_pad, wt0 - nq_pad, rstep, g8, ti8, tfrag, tn, wt, rmt, nullptr, mx, mxe, mxq, flags, w8min, w8max);
+    } else
     for (int rbase = row0; rbase < rows; rbase += kPrepAhead * rstep) {
     float4 vin[kPrepAhead][2];
 #pragma unroll
@@ -3870,6 +4004,7 @@ __global__ void knn_fill_empty_kernel(int* __restrict__ idx, float* __restrict__
 long long* g_trace = nullptr;   // dev diagnostics only
 int g_split_delay_wg = -1;      // test hook: see knn_split_images_kernel
 long long g_split_delay_ticks = 0;
+int g_prep_general = 0;         // test hook: quantised pairs take the general row loop of knn_prep_kernel
 
 struct KnnWs {
     unsigned short* qsplit;       // per-pair arrays: pair b at base + b * stride (elements)
@@ -4150,6 +4285,11 @@ extern "C" int sfm_debug_knn_split_delay(int workgroup, int microseconds) {
     return SFM_OK;
 }
 
+extern "C" int sfm_debug_knn_prep_general(int on) {
+    g_prep_general = on != 0;
+    return SFM_OK;
+}
+
 extern "C" int sfm_debug_set_trace(void* dev_buf) {
     g_trace = static_cast<long long*>(dev_buf);
     return SFM_OK;
@@ -4221,7 +4361,7 @@ int knn_batch_impl(int B, const BatchPtrs& P, int64_t nq, int64_t ldq, int64_t n
                            ratio_counts, 0 /*(the refine kernel writes every count: nothing to zero)*/,
                            p.units, p.tiles, p.G, p.seg_cost, p.n_rb, w.wg_begin, w.rb_first, w.rb_last, p.q4 ? w.wg_sbase : nullptr,
                            w.qi8, w.ti8, w.s_qi8, w.s_ti8, w.wq, w.wt, w.bwmin, w.bwmax, w.rmq, w.rmt, p8.units, p8.G, p8.n_rb, w.wg_begin8, w.rb_first8,
-                           w.rb_last8, w.wg_sbase8, p.q8, w.minfo);
+                           w.rb_last8, w.wg_sbase8, p.q8, w.minfo, g_prep_general);
         SFM_CHECK_LAUNCH();
         hipLaunchKernelGGL(knn_split_images_kernel, dim3(kNormBlocks), dim3(kSplitThreads), 0, stream, P, B, ldq, (int)nq, p.nq_pad, ldt, (int)nt,
                            p.tiles * kTileT, w.qsplit, w.tsplit, w.s_qsplit, w.s_tsplit, w.midflag, w.bmax, p.force_mode,
