@@ -693,6 +693,49 @@ int sfm_mesh_extract(const float* S_dev, const float* W_dev, const float* CWc_de
                      int32_t* faces_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MESH-CLEAN (no reference counterpart; csrc/mesh_clean.hip, docs/mesh.md §7): connected components of a triangle mesh and the
+ * removal of the small ones, after sfm_mesh_extract.  Everything is int32 arithmetic or a bit-for-bit copy; no result depends
+ * on a summation or arrival order; tests/np_mesh_clean.py restates every output exactly.
+ *
+ *   input       vertices_dev [nv][3] float32, optional colors_dev [nv][3] float32, faces_dev [nf][3] int32; 0 <= nv, nf <= 2^31 - 1
+ *   valid face  its three indices lie in 0..nv-1.  An invalid face joins nothing and is never output, and no index outside that
+ *               range is dereferenced.  Repeated indices within a face ((a,a,b), (a,a,a)) and duplicate faces are valid and count.
+ *   components  two vertices are connected when a valid face names both; label[v] = the smallest vertex id of v's component.  A
+ *               vertex in no valid face is its own component with 0 faces.  faces_of[c] = the valid faces whose vertices carry
+ *               label c.
+ *   keep rule   integers min_faces >= 0 and largest_only (0 or 1).  Without largest_only, component c is kept iff
+ *               faces_of[c] >= min_faces.  With it, only the component with the most faces is kept (ties: the lowest label), and
+ *               only if it passes min_faces too.  min_faces = 0, largest_only = 0 keeps everything, face-less vertices included.
+ *   output      kept vertices in their original order, the new id = the rank among the kept vertices; position and colour rows
+ *               copied bit for bit (NaN payloads survive); the valid faces of kept components in their original order, remapped
+ *               to the new ids; counts_dev int32[4] = (vertices kept, faces kept, components, components kept).  The outputs are
+ *               buffers of the input sizes, distinct from the inputs; nothing is written at or past the counted rows.
+ *
+ * sfm_mesh_components — labels by min-label hooking and pointer jumping, at most `rounds` (1..1024) rounds, all enqueued at once.
+ *   labels_dev  [nv] int32.  resume == 0: started from label[v] = v.  resume != 0: continued from the labels given, which must be
+ *               a state an earlier call over the same faces left.
+ *   a round     per valid face m = min(label[a], label[b], label[c]); the three labels and the labels of the three current labels
+ *               are lowered to m (atomic min); per vertex label[v] is lowered to where label[label[..]] leads within 4 hops.
+ *               A round that lowers nothing ends the work: the launches of the later rounds return at once.
+ *   status_dev  int32[2] = (converged 0/1, rounds that lowered a label).  Converged labels are the component minima whatever
+ *               order the atomics landed in.  Unconverged labels are a valid intermediate state: every label is an id of the
+ *               vertex's own component and >= its minimum; call again with resume != 0.
+ * sfm_mesh_clean — labels_dev must be converged labels of these faces (otherwise the outputs are unspecified, though every write
+ *   stays inside the counted rows).  colors_dev and out_colors_dev are both given or both NULL.
+ * Errors (SFM_ERR_ARG, before any device call): negative counts or counts above 2^31 - 1, rounds outside 1..1024, negative
+ *   min_faces, largest_only not 0 or 1, NULL where the count is non-zero (status_dev, counts_dev and the workspace always),
+ *   colours in without colours out or the reverse, a workspace smaller than the _ws_bytes twin says.
+ * The _ws_bytes twins return 0 for invalid sizes.
+ * ---------------------------------------------------------------------- */
+size_t sfm_mesh_components_ws_bytes(int64_t nv, int64_t nf);
+int sfm_mesh_components(const int32_t* faces_dev, int64_t nv, int64_t nf, int rounds, int resume, int32_t* labels_dev, int32_t* status_dev,
+                        void* ws_dev, size_t ws_bytes, void* stream);
+size_t sfm_mesh_clean_ws_bytes(int64_t nv, int64_t nf);
+int sfm_mesh_clean(const float* vertices_dev, const float* colors_dev, const int32_t* faces_dev, int64_t nv, int64_t nf,
+                   const int32_t* labels_dev, int64_t min_faces, int largest_only, float* out_vertices_dev, float* out_colors_dev,
+                   int32_t* out_faces_dev, int32_t* counts_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets
  * its dominant kernels with hipEvents recorded on the launch stream.
  * sfm_profile_read synchronises those events, returns the summed device time

@@ -4,6 +4,8 @@ the dense cloud; the reference's `camera_orientation` writes triangle meshes wit
 Thin, validating wrappers over `sfm_tsdf_integrate`, `sfm_mesh_count` and `sfm_mesh_extract` (include/sfm_hip.h, "MESH"): device
 tensors in, device tensors out, stream ordered, no CPU path.  The host part is the choice of the volume from the fused cloud
 (float64) and the cast of the cameras' projection matrices.  docs/mesh.md describes the algorithm and its numbers.
+Opt-in after the extraction: `mesh_components` / `clean_mesh` (sfm_mesh_components, sfm_mesh_clean; "MESH-CLEAN") drop the small
+connected components, `run_mesh(clean=True)` (docs/mesh.md §7).
 """
 import numpy as np
 import torch
@@ -18,6 +20,10 @@ MAX_POINTS = 1 << 27            # lattice points per grid
 # (docs/mesh.md, "Calibration").
 TRUNC_VOXELS = 2.0              # truncation distance in voxels
 W_MIN = 3.0                     # observations a lattice point needs to be known
+
+# Clean-up (include/sfm_hip.h, "MESH-CLEAN"; docs/mesh.md §7).
+COMPONENT_ROUNDS = 24           # labelling rounds enqueued per call: twice the most any measured mesh needed (docs/mesh.md §7)
+MIN_COMPONENT_SHARE = 1.0 / 512 # run_mesh(clean=True) drops components with fewer faces than this share of all faces
 
 
 def volume_bounds(points, resolution=256, pad=0.05):
@@ -145,8 +151,78 @@ def extract_mesh(S, W, C, origin, voxel, w_min=W_MIN, packed=False):
     return (verts, cols, faces, buf) if packed else (verts, cols, faces)
 
 
+def _faces(faces, what):
+    require_cuda(faces)
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise SfmHipError(f"{what}: faces must be a [k, 3] int32 device tensor")
+    return faces.contiguous()
+
+
+def mesh_components(faces, nv, rounds=COMPONENT_ROUNDS, labels=None, status=None):
+    """sfm_mesh_components: label[v] = the smallest vertex id of v's connected component, at most `rounds` (1..1024) rounds.
+    faces [k, 3] int32 device tensor (indices outside 0..nv-1 make a face invalid: it joins nothing); labels: an int32 [nv] device
+    tensor an earlier call left, to continue from (updated in place).  Returns (labels, status): status an int32 [2] device tensor
+    (converged 0/1, rounds that lowered a label; written into `status` when given).  No host wait."""
+    from .ops import _workspace
+    faces = _faces(faces, "mesh_components")
+    nv, nf, dev = int(nv), int(faces.shape[0]), faces.device
+    resume = labels is not None
+    if resume:
+        require_cuda(labels)
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (nv,) or not labels.is_contiguous() or labels.device != dev:
+            raise SfmHipError("mesh_components: labels must be a contiguous int32 [nv] tensor on the faces' device")
+    else:
+        labels = torch.empty(max(nv, 0), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty(2, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_mesh_components_ws_bytes(max(nv, 0), nf))
+    with on_device(dev):
+        check(L.sfm_mesh_components(ptr(faces) if nf else None, nv, nf, int(rounds), int(resume), ptr(labels) if nv > 0 else None, ptr(status),
+                                    ptr(ws), ws.numel(), stream_ptr()), "sfm_mesh_components")
+    return labels, status
+
+
+def clean_mesh(vertices, colors, faces, min_faces=1, largest_only=False, packed=False, rounds=COMPONENT_ROUNDS, labels=None):
+    """Drop the small connected components of a mesh (sfm_mesh_components, then sfm_mesh_clean); no host wait.
+    vertices [m, 3] float32, colors [m, 3] float32 or None, faces [k, 3] int32: device tensors.  Component c is kept iff it has at
+    least `min_faces` faces (0 keeps everything, 1 drops the vertices no face names); largest_only keeps only the component with
+    the most faces (ties: the lowest vertex id), if it passes min_faces.  labels: labels an earlier call left, to continue from.
+    Returns (vertices, colors or None, faces, counts): tensors of the INPUT sizes of which the first counts[0] / counts[1] rows are
+    the result (kept vertices in their order, rows bit for bit; kept faces in their order, renumbered) and the rest is not
+    written; counts an int32 [4] device tensor (vertices kept, faces kept, components, components kept).  The counts are
+    meaningful once the labelling has converged (status[0] == 1; otherwise call again with labels=labels).
+    packed=True: returns (vertices, colors, faces, counts, status, labels, buf) with buf the one int32 buffer that holds counts [4],
+    status [2], vertices, colours and faces in that order, so that a caller downloads once and slices on the host."""
+    from .ops import _workspace
+    require_cuda(vertices, colors)
+    faces = _faces(faces, "clean_mesh")
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise SfmHipError("clean_mesh: vertices must be an [m, 3] float32 device tensor")
+    if colors is not None and (colors.dtype != torch.float32 or colors.shape != vertices.shape):
+        raise SfmHipError("clean_mesh: colors must be [m, 3] float32 like the vertices")
+    vertices = vertices.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    ncol = nv if colors is not None else 0
+    buf = torch.empty(6 + 3 * nv + 3 * ncol + 3 * nf, dtype=torch.int32, device=dev)
+    counts, status = buf[:4], buf[4:6]
+    out_v = buf[6:6 + 3 * nv].view(torch.float32).view(nv, 3)
+    out_c = buf[6 + 3 * nv:6 + 3 * (nv + ncol)].view(torch.float32).view(ncol, 3) if colors is not None else None
+    out_f = buf[6 + 3 * (nv + ncol):].view(nf, 3)
+    labels, _ = mesh_components(faces, nv, rounds, labels, status=status)
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_mesh_clean_ws_bytes(nv, nf))
+    with on_device(dev):
+        check(L.sfm_mesh_clean(ptr(vertices) if nv else None, ptr(colors) if ncol else None, ptr(faces) if nf else None, nv, nf,
+                               ptr(labels) if nv else None, int(min_faces), int(bool(largest_only)), ptr(out_v) if nv else None,
+                               ptr(out_c) if ncol else None, ptr(out_f) if nf else None, ptr(counts), ptr(ws), ws.numel(), stream_ptr()),
+              "sfm_mesh_clean")
+    return (out_v, out_c, out_f, counts, status, labels, buf) if packed else (out_v, out_c, out_f, counts)
+
+
 def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOXELS, w_min=W_MIN, tau=0.01, min_consistent=2, nsrc=4,
-             pad=0.05):
+             pad=0.05, clean=False, min_component_share=MIN_COMPONENT_SHARE, min_component_faces=None, largest_only=False):
     """A coloured triangle mesh of a registered sequence from run_mvs's depth maps.
 
     images:  the BGR uint8 frames run_mvs got (device tensors or host arrays, K's resolution, posearr's camera order)
@@ -154,8 +230,12 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     Per view a consistency mask (mvs.consistency with unique=False: every pixel >= `min_consistent` of its `nsrc` sequence
     neighbours agree with, within `tau`), then one sfm_tsdf_integrate over all views (truncation `trunc_voxels` voxels),
     marching tetrahedra over the points seen `w_min` times.  Defaults: docs/mesh.md, "Calibration".
+    clean=True: then the connected components with fewer than `min_component_faces` faces are dropped (clean_mesh; None:
+    max(1, floor(min_component_share * faces)); largest_only: all but the largest), and the dict gains `components` and
+    `components_kept`.
     Returns dict(vertices (m, 3) float64, colors (m, 3) float64 B G R, faces (k, 3) int32) for pipeline.to_ply_mesh.
-    Two host waits per call: the mesh totals and the one download; every upload is stream-ordered (pinned memory)."""
+    Two host waits per call: the mesh totals and the one download; every upload is stream-ordered (pinned memory).  (Should the
+    downloaded labelling status say "not converged" the labelling is continued, and cleaned and downloaded again, until it has.)"""
     from . import mvs
     K = np.asarray(K, np.float64).reshape(3, 3)
     Ps = np.asarray(posearr, np.float64)[9:].reshape(-1, 3, 4)
@@ -190,8 +270,33 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
         S, W, C = tsdf_integrate(torch.stack(depths), projection_rows(K, Ps), origin, voxel, dims, float(trunc_voxels) * voxel,
                                  masks=masks, bgr=frames)
         verts, cols, faces, buf = extract_mesh(S, W, C, origin, voxel, w_min, packed=True)
+        if clean:
+            return _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only)
         host = buf.cpu().numpy()                                    # the one download
     nv, nt = len(verts), len(faces)
     fl = host[:6 * nv].view(np.float32)
     return dict(vertices=fl[:3 * nv].reshape(nv, 3).astype(np.float64), colors=fl[3 * nv:].reshape(nv, 3).astype(np.float64),
                 faces=np.ascontiguousarray(host[6 * nv:].reshape(nt, 3)))
+
+
+def _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only):
+    """run_mesh's tail with clean=True: the cleaned mesh in one download."""
+    nv, nt = len(verts), len(faces)
+    if min_component_faces is None:
+        if not (0.0 <= float(min_component_share) <= 1.0):
+            raise SfmHipError(f"run_mesh: min_component_share {min_component_share} must lie in 0..1")
+        min_faces = max(1, int(np.floor(float(min_component_share) * nt)))
+    else:
+        min_faces = int(min_component_faces)
+        if min_faces < 0:
+            raise SfmHipError(f"run_mesh: min_component_faces {min_faces} is negative")
+    labels = None
+    while True:
+        *_, labels, buf = clean_mesh(verts, cols, faces, min_faces, largest_only, packed=True, labels=labels)
+        host = buf.cpu().numpy()                                    # the one download
+        if host[4]:                                                 # converged; otherwise every batch of rounds lowers a label
+            break
+    kv, kf, ncomp, nkept = (int(v) for v in host[:4])
+    fl = host[6:6 + 6 * nv].view(np.float32)
+    return dict(vertices=fl[:3 * kv].reshape(kv, 3).astype(np.float64), colors=fl[3 * nv:3 * (nv + kv)].reshape(kv, 3).astype(np.float64),
+                faces=np.ascontiguousarray(host[6 + 6 * nv:6 + 6 * nv + 3 * kf].reshape(kf, 3)), components=ncomp, components_kept=nkept)
