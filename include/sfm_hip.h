@@ -759,6 +759,10 @@ int sfm_debug_knn_split_delay(int workgroup, int microseconds);
 /* Test hook: with on != 0 every following knn_prep_kernel launch sends pairs that are quantised for the integer body through the
  * GENERAL row loop instead of the lean one (tests/test_gpu_knn_prep_lean.py: both must leave the same words).  0 switches it off. */
 int sfm_debug_knn_prep_general(int on);
+/* Test hook: every following knn_prep_kernel launch runs `n` (1 .. 256) row workgroups per pair instead of the number the library
+ * derives from the batch size (256 up to four pairs, then as many as fill one resident round: 128 for eight); 0 restores the rule.
+ * Results do not depend on it (tests/test_gpu_knn_prep_blocks.py); it also serves same-box timing comparisons. */
+int sfm_debug_knn_prep_blocks(int n);
 int sfm_profile_read(int slot, double* total_ms_host, int64_t* launches_host);
 /* How often library calls of this process have WAITED for the device so far (cumulative; the RANSAC entry points read the
  * hypothesis scores back chunk by chunk, the Schur solver its convergence scalars).  Diagnostics: bench.py reports the

@@ -614,6 +614,29 @@ __device__ __forceinline__ int lane_xor(int v) {
 }
 template <int M>
 __device__ __forceinline__ float lane_xor(float v) { return __int_as_float(lane_xor<M>(__float_as_int(v))); }
+// Reduction over the 64 lanes of a wave (every lane active; every lane returns the result) with no trip through the LDS
+// crossbar and no address register: lane ^ 32 and lane ^ 16 by v_permlane32_swap / v_permlane16_swap (gfx950: the upper half /
+// the odd rows of sixteen of the first operand change places with the lower half / the even rows of the second; with both
+// operands the same value, the pair of results holds {own, partner} in the lower lanes), lane ^ 8 .. ^ 1 by DPP row rotations
+// (after the step by m the value has period m within its row, so lane + m (mod 16) holds what lane ^ m holds).  The same
+// pairs meet in the same order as in the `v = op(v, __shfl_xor(v, m))` butterfly over m = 32, 16, .., 1, so for a commutative
+// op — float addition included — the result is that butterfly's, bit for bit.
+template <typename V, typename Op>
+__device__ __forceinline__ V wave64_reduce(V v, Op op) {
+    static_assert(sizeof(V) == 4, "one register");
+    const auto r32 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
+    v = op(__builtin_bit_cast(V, (unsigned)r32[0]), __builtin_bit_cast(V, (unsigned)r32[1]));
+    const auto r16 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
+    v = op(__builtin_bit_cast(V, (unsigned)r16[0]), __builtin_bit_cast(V, (unsigned)r16[1]));
+    auto rot = [](V x, auto ctrl) {
+        return __builtin_bit_cast(V, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + decltype(ctrl)::value /*row_ror*/, 0xF, 0xF, true));
+    };
+    v = op(v, rot(v, std::integral_constant<int, 8>{}));
+    v = op(v, rot(v, std::integral_constant<int, 4>{}));
+    v = op(v, rot(v, std::integral_constant<int, 2>{}));
+    v = op(v, rot(v, std::integral_constant<int, 1>{}));
+    return v;
+}
 // Wave-uniform mode from the per-block flags and per-block max ||t||^2 (256 entries each).
 __device__ __forceinline__ int knn_filter_mode(const int* __restrict__ flags, const float* __restrict__ bmax, int lane,
                                                float* tmax_out = nullptr) {
@@ -714,24 +737,24 @@ __device__ __forceinline__ Q8Grid q8_sample_grid(const float* __restrict__ Q, in
     const float4 v2 = *reinterpret_cast<const float4*>(ts), v3 = *reinterpret_cast<const float4*>(ts + 4);
     const float in[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
     float mn = kInf, mx = -kInf, sm = 0.f, sq = 0.f;
-    bool bad = false, nonu8 = false;
+    // The two flags of the sample — "some value is NaN / inf" and "some value is not an integer 0 .. 255" — cost no test per
+    // element beyond the integrality compare (the kernel is bound by its vector-ALU instruction count, and every workgroup of
+    // the pair pays for this sample): the RANGE half of the second is read off the sample's min / max below (NaN fails the
+    // integrality compare), and the first off the sample's sum — see there.
+    bool frac = false;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         mn = fminf(mn, in[e]);
         mx = fmaxf(mx, in[e]);
         sm += in[e];
         sq = fmaf(in[e], in[e], sq);
-        bad = bad || !(fabsf(in[e]) < kInf);                            // NaN / inf
-        nonu8 = nonu8 || !(in[e] >= 0.f && in[e] <= 255.f && in[e] == floorf(in[e]));
+        frac = frac || in[e] != floorf(in[e]);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, m, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-        sm += __shfl_xor(sm, m, 64);
-        sq += __shfl_xor(sq, m, 64);
-    }
-    const int fl = (__any(bad) ? 1 : 0) | (__any(nonu8) ? 2 : 0);
+    mn = wave64_reduce(mn, [](float a, float b) { return fminf(a, b); });
+    mx = wave64_reduce(mx, [](float a, float b) { return fmaxf(a, b); });
+    sm = wave64_reduce(sm, [](float a, float b) { return a + b; });
+    sq = wave64_reduce(sq, [](float a, float b) { return a + b; });
+    const int fl = __any(frac) ? 2 : 0;
     __syncthreads();                                                    // (a caller may loop: the previous round's reads are done)
     if ((threadIdx.x & 63) == 0) {
         red[5 * (threadIdx.x >> 6)] = mn;
@@ -751,6 +774,11 @@ __device__ __forceinline__ Q8Grid q8_sample_grid(const float* __restrict__ Q, in
         sm += red[5 * w + 3];
         sq += red[5 * w + 4];
     }
+    // NaN / inf: a sum that holds one is NaN or inf and stays so.  A sum of 4096 FINITE values can overflow only when some
+    // |value| >= FLT_MAX / 4096 = 8.3e34: such a sample is no u8 sample, and its step (max - min) / 255 would have to be
+    // >= 2^-16 x 8.3e34 > 1e30 to pass the rule below, which caps it at 1e30 — kind 2 either way, and kind 2 carries no grid.
+    if (!(fabsf(sm) < kInf)) flw |= 1;
+    if (!(mn >= 0.f && mx <= 255.f)) flw |= 2;                          // (-0 counts as 0; an all-NaN sample has flag 1)
     Q8Grid g{0.f, 1.f, 1.f, 0};
     if (flw & 1) { g.kind = 2; return g; }
     if (!(flw & 2)) return g;                                           // u8 integers as far as the sample goes
@@ -903,6 +931,9 @@ __device__ __forceinline__ void prep_lean_rows(const float* __restrict__ src, in
             // (uniform offsets: the wave's tile and its four rows' place in it; 32-bit as everywhere for the fragment images)
             const unsigned tile = (unsigned)wr >> 5, rin = (unsigned)wr & 31u;
             if constexpr (!kIsQ) {
+                // (NOT dead while the pair stays quantised only: the repair of knn_split_images_kernel rewrites the eight fp16
+                // fragments of a tile, never this ninth one, and the 16-bit bodies that run after a repair read it from here —
+                // knn_filter_q4_kernel's `tile * kTileFragBytes + 8 * kFragBytes` load.  So the write stays.)
                 unsigned char* fbase = tfrag + (tile * (unsigned)kTileFragBytes + (8u * kFragBytes + (rin << 3)));
                 if (c < 2) *reinterpret_cast<uint2*>(fbase + fragoff) = frag_init_operand(nrm, false, c);
             }
@@ -938,8 +969,9 @@ __device__ __forceinline__ void prep_lean_rows(const float* __restrict__ src, in
 // Image layout: [3][n_pad][128] 16-bit: bf16 hi, bf16 mid, fp16; the two bf16 planes are only needed by the split
 // arithmetic (values outside fp16's range) and are written by knn_split_images_kernel, which runs when the flags say so:
 // the common case moves 15 MB per 10k x 10k pair instead of 25.
-// Batched: grid = (blocks + 1, B); column b works on pair b (its workspace arrays sit at b * stride).
-constexpr int kPrepThreads = 256;      // one wave per SIMD, 103 registers (the general row loop's; docs/knn.md): a prep workgroup of the NEXT launch set fits beside the q4 filter's 380-register waves
+// Batched: grid = (blocks + 2, B), blocks = prep_blocks(B) <= kNormBlocks row workgroups per pair and two for the partition
+// tables; column b works on pair b (its workspace arrays sit at b * stride).
+constexpr int kPrepThreads = 256;      // one wave per SIMD, 102 registers (the general row loop's; docs/knn.md): a prep workgroup of the NEXT launch set fits beside the q4 filter's 380-register waves
 __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int64_t ldq, int nq, int nq_pad,
                                                        int64_t ldt, int nt, int nt_pad,
                                                        unsigned short* __restrict__ qsplit, float* __restrict__ qn,
@@ -1159,23 +1191,19 @@ __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int
         }
     }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-        mxe = fmaxf(mxe, __shfl_xor(mxe, m, 64));
-        mxq = fmaxf(mxq, __shfl_xor(mxq, m, 64));
-    }
-    int wfl = 0;
-#pragma unroll
-    for (int b = 1; b <= kFlagQ8; b <<= 1) wfl |= __any((flags & b) != 0) ? b : 0;
+    // The wave's words, with no trip through the LDS crossbar (wave64_reduce).  mx, mxe and mxq are maxima of squared norms and
+    // residuals: +0 .. +inf, never NaN (fmaxf drops one) and never -0, so their order is the order of their bit patterns — an integer
+    // max, which needs no canonicalising pass over its operands.  The flag word is ONE OR-reduction.
+    auto umax = [](unsigned a, unsigned b) { return max(a, b); };
+    mx = __uint_as_float(wave64_reduce(__float_as_uint(mx), umax));
+    mxe = __uint_as_float(wave64_reduce(__float_as_uint(mxe), umax));
+    mxq = __uint_as_float(wave64_reduce(__float_as_uint(mxq), umax));
+    const int wfl = (int)wave64_reduce(flags, [](unsigned a, unsigned b) { return a | b; });
     __shared__ float wmaxe[kPrepWaves], wmaxq[kPrepWaves];
     __shared__ int w8lo[kPrepWaves], w8hi[kPrepWaves];
     if (do8) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            w8min = min(w8min, __shfl_xor(w8min, m, 64));
-            w8max = max(w8max, __shfl_xor(w8max, m, 64));
-        }
+        w8min = wave64_reduce(w8min, [](int a, int b) { return min(a, b); });
+        w8max = wave64_reduce(w8max, [](int a, int b) { return max(a, b); });
     }
     if ((threadIdx.x & 63) == 0) {
         wmax[threadIdx.x >> 6] = mx;
@@ -1205,6 +1233,17 @@ __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int
         if (blockIdx.x == 0 && stats) stats[0] = 0;   // rescanned-query counter (refine kernel)
         if (blockIdx.x == 1 || nblk == 1)
             for (int i = 0; i < nzero; ++i) zero[i] = 0;   // Lowe-ratio survivor counters of the fused match call
+    }
+    // The per-block arrays have kNormBlocks entries per pair and their readers (knn_filter_mode, knn_split_images_kernel's
+    // reduce_modes, the refine kernel) reduce all of them; a launch with fewer workgroups (the host sizes the grid by the batch)
+    // leaves the NEUTRAL words — those of a workgroup without rows — in the entries nobody owns: workgroup x those at
+    // x + nblk, x + 2 nblk, ...  (The workspace is not cleared between calls, and an earlier call may have run with more blocks.)
+    for (int e = blockIdx.x + nblk * (1 + (int)threadIdx.x); e < kNormBlocks; e += nblk * kPrepThreads) {
+        bmax[e] = 0.f;
+        bmaxerr[e] = 0.f;
+        bqmax[e] = 0.f;
+        midflag[e] = 0;
+        if (do8) { bwmin[e] = INT_MAX; bwmax[e] = INT_MIN; }
     }
 }
 
@@ -1327,9 +1366,12 @@ __global__ __launch_bounds__(kSplitThreads) void knn_split_images_kernel(BatchPt
     if (ti8 && q8any && !i8) {
         // REPAIR: some pair was quantised by the prep pass (byte image only) but the batch runs a 16-bit body after all — the
         // grid did not fit, the init product's range is exceeded, or another pair of the batch is not integer-body material.
-        // Those pairs get their fp16 image, residuals and flags now, from the original floats.  Rows are dealt exactly as in the
-        // prep launch (workgroup x of kNormBlocks, sixteen lanes per row), so workgroup x simply REWRITES the pair's per-block
-        // words x.  Rare by construction (the sample rule), so it only has to be right.
+        // Those pairs get their fp16 image, residuals and flags now, from the original floats.  Rows are dealt over the
+        // kNormBlocks workgroups of THIS launch, sixteen lanes per row — the prep launch's dealing when it runs kNormBlocks row
+        // workgroups, another one when its grid is sized by the batch (prep_blocks).  That does not matter: workgroup x writes
+        // shadow word x, the last workgroup out REPLACES all kNormBlocks midflag / bmaxerr words of a repaired pair by the shadow
+        // words (whatever grid wrote the old ones, neutral entries included), and the words the repair leaves alone — bmax, bqmax,
+        // bwmin, bwmax — are only ever folded by max / min over all entries.  Rare by construction (the sample rule), so it only has to be right.
         __shared__ int rfl[kSplitThreads / 64];
         __shared__ float rme[kSplitThreads / 64];
         const int c = threadIdx.x & 15, rows = nq_pad + nt_pad;
@@ -4005,6 +4047,17 @@ long long* g_trace = nullptr;   // dev diagnostics only
 int g_split_delay_wg = -1;      // test hook: see knn_split_images_kernel
 long long g_split_delay_ticks = 0;
 int g_prep_general = 0;         // test hook: quantised pairs take the general row loop of knn_prep_kernel
+int g_prep_blocks = 0;          // test hook: row workgroups per pair of knn_prep_kernel (0: prep_blocks' rule)
+
+// Row workgroups per pair of the prep launch.  Every workgroup pays a fixed part — the quantisation sample, the prologue, the
+// reductions at its end — that does not shrink with its share of the rows, so the launch gets no more workgroups than fill ONE
+// resident round: four 4-wave workgroups per CU (kResidentWaves), shared among the pairs of the batch.  Small batches keep all
+// kNormBlocks: a single pair's latency and the large shapes are bound by the rows, not by the fixed part.
+int prep_blocks(int B) {
+    if (g_prep_blocks > 0) return g_prep_blocks;
+    constexpr int kRound = kResidentWaves / (kPrepThreads / 64);
+    return std::min(kNormBlocks, (kRound + B - 1) / B);
+}
 
 struct KnnWs {
     unsigned short* qsplit;       // per-pair arrays: pair b at base + b * stride (elements)
@@ -4290,6 +4343,12 @@ extern "C" int sfm_debug_knn_prep_general(int on) {
     return SFM_OK;
 }
 
+extern "C" int sfm_debug_knn_prep_blocks(int n) {
+    SFM_CHECK_ARG(n >= 0 && n <= kNormBlocks, "sfm_debug_knn_prep_blocks: 0 (the rule) or 1 .. %d workgroups per pair (got %d)", kNormBlocks, n);
+    g_prep_blocks = n;
+    return SFM_OK;
+}
+
 extern "C" int sfm_debug_set_trace(void* dev_buf) {
     g_trace = static_cast<long long*>(dev_buf);
     return SFM_OK;
@@ -4355,7 +4414,7 @@ int knn_batch_impl(int B, const BatchPtrs& P, int64_t nq, int64_t ldq, int64_t n
     const int prof_reps = p.split ? sfm::prof_repeat() : 1;
     static const int abl = dev_env_int("SFM_KNN_ABL", 0);       // timing ablations (WRONG results): dev builds only
     if (p.split) {
-        hipLaunchKernelGGL(knn_prep_kernel, dim3(kNormBlocks + 2, (unsigned)B), dim3(kPrepThreads), 0, stream, P, ldq, (int)nq, p.nq_pad, ldt, (int)nt,
+        hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)prep_blocks(B) + 2, (unsigned)B), dim3(kPrepThreads), 0, stream, P, ldq, (int)nq, p.nq_pad, ldt, (int)nt,
                            p.tiles * kTileT, w.qsplit, w.qn, w.tsplit, w.tn, w.bmax, w.midflag, w.qerr, w.bmaxerr, w.bqmax, w.s_qsplit, w.s_tsplit, w.s_qn, w.s_tn,
                            p.q4 ? w.qfrag : nullptr, w.tfrag, w.s_qfrag, w.s_tfrag,
                            ratio_counts, 0 /*(the refine kernel writes every count: nothing to zero)*/,
