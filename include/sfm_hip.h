@@ -736,6 +736,55 @@ int sfm_mesh_clean(const float* vertices_dev, const float* colors_dev, const int
                    int32_t* out_faces_dev, int32_t* counts_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MESH-FINISH (no reference counterpart; csrc/mesh_finish.hip, docs/mesh.md §8): vertex normals and Taubin smoothing of a triangle
+ * mesh, after sfm_mesh_extract or sfm_mesh_clean.  Every sum over faces is an int64 sum of quantised terms, so no result depends
+ * on the order in which atomics land or on whether an implementation scatters or gathers; every float32 and float64 operation is
+ * correctly rounded in the order written here (no FMA, no reassociation); int64 -> float64 rounds to nearest even.
+ * tests/np_mesh_finish.py restates both outputs bit for bit.
+ *
+ *   input       vertices_dev [nv_cap][3] float32, faces_dev [nf_cap][3] int32; 0 <= nv_cap, nf_cap <= 2^31 - 1
+ *   counts_dev  optional int32[2] = (nv, nf), READ ON THE DEVICE (the first two words of sfm_mesh_clean's counts are this pair, so
+ *               the call follows it on the stream with no host wait).  NULL: nv = nv_cap, nf = nf_cap.  A count that is negative
+ *               or above its capacity is taken as the capacity.
+ *   valid face  one of the first nf faces whose three indices lie in 0..nv-1.  Anything else contributes nothing, and no index
+ *               outside that range is dereferenced.  Repeated indices and duplicate faces follow the formulas, no special case.
+ *   output      [nv_cap][3] float32, distinct from the input; rows at or past nv are never written.
+ *
+ * sfm_mesh_normals — normals_dev.  Per valid face (i0, i1, i2) with positions a, b, c:
+ *     e1 = b - a, e2 = c - a per coordinate;
+ *     n_x = e1_y*e2_z - e1_z*e2_y,  n_y = e1_z*e2_x - e1_x*e2_z,  n_z = e1_x*e2_y - e1_y*e2_x  (the right-hand normal: outward by
+ *     the winding sfm_mesh_extract guarantees);  len = sqrtf((n_x*n_x + n_y*n_y) + n_z*n_z);
+ *     the face contributes iff len is finite and > 0:  u_c = n_c / len,  q_c = (int64) rintf(u_c * 2^30);  q is added to the
+ *     accumulator of each of its three corners, once per corner (a repeated index adds twice).
+ *   Per vertex: d_c = (double) acc_c;  L = sqrt((d_x*d_x + d_y*d_y) + d_z*d_z);  normal_c = (float)(d_c / L), or (0, 0, 0) when
+ *   L == 0.  This is the equal-weight sum of unit face normals (open3d's compute_vertex_normals), normalised.
+ *
+ * sfm_mesh_smooth — out_vertices_dev after nsteps (0..64) steps; factors_host float32 [nsteps] (finite), origin_host float32 [3]
+ *   = o (finite), pscale > 0 (finite; the wrapper passes a power of two).  Step s maps positions p to p':
+ *     r_c = rintf((p_c - o_c) * pscale);  a vertex is USABLE iff all three |r_c| <= 2^30 (NaN fails);
+ *     for every valid face and each of its corners k, each of the OTHER two corners j that is usable adds (int64) r(j) to acc[i_k]
+ *     and 1 to cnt[i_k] (int64);
+ *     a vertex moves iff it is usable and cnt > 0:  m_c = ((double)acc_c / (double)cnt) / (double)pscale + (double)o_c,
+ *     p'_c = (float)((double)p_c + (double)factor[s] * (m_c - (double)p_c));  every other vertex keeps its row bit for bit
+ *     (NaN payloads included).
+ *   This is the face-umbrella Laplacian: an edge shared by two faces counts twice, a boundary edge once.  Taubin smoothing is the
+ *   factor sequence lambda, mu, lambda, mu, ... with lambda > 0 > mu.  nsteps = 0 copies the counted rows.  The steps ping-pong
+ *   through the workspace; the last one lands in the output.
+ * Errors (SFM_ERR_ARG, before any device call): a capacity negative or above 2^31 - 1, NULL where a capacity is non-zero (vertices,
+ *   the output and the workspace with nv_cap; faces with nf_cap; origin_host always; factors_host with nsteps), the output equal to
+ *   the input pointer, a workspace smaller than the _ws_bytes twin says; sfm_mesh_smooth also nsteps outside 0..64, a factor or an
+ *   origin coordinate that is not finite, pscale not finite or not positive.
+ * The _ws_bytes twins return 0 for invalid sizes (32 bytes per vertex; smoothing 24 more).
+ * ---------------------------------------------------------------------- */
+size_t sfm_mesh_normals_ws_bytes(int64_t nv_cap, int64_t nf_cap);
+int sfm_mesh_normals(const float* vertices_dev, const int32_t* faces_dev, int64_t nv_cap, int64_t nf_cap, const int32_t* counts_dev,
+                     float* normals_dev, void* ws_dev, size_t ws_bytes, void* stream);
+size_t sfm_mesh_smooth_ws_bytes(int64_t nv_cap, int64_t nf_cap);
+int sfm_mesh_smooth(const float* vertices_dev, const int32_t* faces_dev, int64_t nv_cap, int64_t nf_cap, const int32_t* counts_dev, int nsteps,
+                    const float* factors_host, const float* origin_host, float pscale, float* out_vertices_dev, void* ws_dev,
+                    size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets
  * its dominant kernels with hipEvents recorded on the launch stream.
  * sfm_profile_read synchronises those events, returns the summed device time

@@ -5,7 +5,8 @@ Thin, validating wrappers over `sfm_tsdf_integrate`, `sfm_mesh_count` and `sfm_m
 tensors in, device tensors out, stream ordered, no CPU path.  The host part is the choice of the volume from the fused cloud
 (float64) and the cast of the cameras' projection matrices.  docs/mesh.md describes the algorithm and its numbers.
 Opt-in after the extraction: `mesh_components` / `clean_mesh` (sfm_mesh_components, sfm_mesh_clean; "MESH-CLEAN") drop the small
-connected components, `run_mesh(clean=True)` (docs/mesh.md §7).
+connected components, `run_mesh(clean=True)` (docs/mesh.md §7); `smooth_mesh` / `mesh_normals` (sfm_mesh_smooth, sfm_mesh_normals;
+"MESH-FINISH") smooth the surface and give it vertex normals, `run_mesh(smooth=..., normals=True)` (docs/mesh.md §8).
 """
 import numpy as np
 import torch
@@ -24,6 +25,11 @@ W_MIN = 3.0                     # observations a lattice point needs to be known
 # Clean-up (include/sfm_hip.h, "MESH-CLEAN"; docs/mesh.md §7).
 COMPONENT_ROUNDS = 24           # labelling rounds enqueued per call: twice the most any measured mesh needed (docs/mesh.md §7)
 MIN_COMPONENT_SHARE = 1.0 / 512 # run_mesh(clean=True) drops components with fewer faces than this share of all faces
+
+# Finishing (include/sfm_hip.h, "MESH-FINISH"; docs/mesh.md §8).
+SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53   # Taubin's pair: the pass band ends at 1/lambda + 1/mu = 0.113
+MAX_SMOOTH_STEPS = 32           # pairs: sfm_mesh_smooth takes 64 steps
+SMOOTH_PAIRS = 10               # the pair count the calibration recommends (docs/mesh.md §8); run_mesh's own default stays 0
 
 
 def volume_bounds(points, resolution=256, pad=0.05):
@@ -221,8 +227,84 @@ def clean_mesh(vertices, colors, faces, min_faces=1, largest_only=False, packed=
     return (out_v, out_c, out_f, counts, status, labels, buf) if packed else (out_v, out_c, out_f, counts)
 
 
+def _finish_args(vertices, faces, counts, what):
+    require_cuda(vertices, counts)
+    faces = _faces(faces, what)
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise SfmHipError(f"{what}: vertices must be an [m, 3] float32 device tensor")
+    if faces.device != vertices.device:
+        raise SfmHipError(f"{what}: vertices and faces must live on one device")
+    if counts is not None and (counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() < 2 or not counts.is_contiguous()
+                               or counts.device != vertices.device):
+        raise SfmHipError(f"{what}: counts must be a contiguous int32 device tensor that starts with (vertices, faces)")
+    return vertices.contiguous(), faces
+
+
+def mesh_normals(vertices, faces, counts=None, out=None):
+    """Vertex normals (sfm_mesh_normals): the normalised equal-weight sum of the unit normals of the faces at each vertex, outward
+    by extract_mesh's winding; (0, 0, 0) at a vertex no face with an area names.  vertices [m, 3] float32, faces [k, 3] int32
+    device tensors; counts: an int32 device tensor whose first two words are the numbers of rows in use (clean_mesh's counts),
+    read on the device.  Returns an [m, 3] float32 device tensor (written into `out` when given) of which the counted rows are
+    written.  No host wait; the words do not depend on the order of the faces."""
+    from .ops import _workspace
+    vertices, faces = _finish_args(vertices, faces, counts, "mesh_normals")
+    nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    if out is None:
+        out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (nv, 3) or not out.is_contiguous() or out.device != dev:
+        raise SfmHipError("mesh_normals: out must be a contiguous [m, 3] float32 tensor on the vertices' device")
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_mesh_normals_ws_bytes(nv, nf))
+    with on_device(dev):
+        check(L.sfm_mesh_normals(ptr(vertices) if nv else None, ptr(faces) if nf else None, nv, nf, ptr(counts), ptr(out) if nv else None,
+                                 ptr(ws), ws.numel(), stream_ptr()), "sfm_mesh_normals")
+    return out
+
+
+def smooth_scale(extent):
+    """pscale of smooth_mesh: the largest power of two with extent * pscale <= 2^29 (positions are quantised to 1 / pscale; the
+    factor 2 of head-room up to the 2^30 a usable vertex may reach keeps vertices that drift slightly outside the frame usable)."""
+    extent = float(extent)
+    if not (np.isfinite(extent) and extent > 0.0):
+        raise SfmHipError(f"smooth_mesh: extent {extent} must be finite and positive")
+    e = int(np.floor(np.log2(2.0 ** 29 / extent)))
+    while extent * 2.0 ** (e + 1) <= 2.0 ** 29:
+        e += 1
+    while extent * 2.0 ** e > 2.0 ** 29:
+        e -= 1
+    return float(2.0 ** min(max(e, -126), 127))
+
+
+def smooth_mesh(vertices, faces, steps, origin, extent, lam=SMOOTH_LAMBDA, mu=SMOOTH_MU, counts=None, out=None):
+    """Taubin smoothing (sfm_mesh_smooth): `steps` (0..32) PAIRS of face-umbrella Laplacian steps with the factors lam, mu, lam,
+    mu, ...  Positions are quantised relative to `origin` ((3,), the frame's corner) at the largest power-of-two scale that fits
+    `extent` (its longest side) into 2^29; a vertex further than twice the extent from the origin, or not finite, neither moves nor
+    pulls its neighbours.  counts as in mesh_normals.  Returns an [m, 3] float32 device tensor (`out` when given) of which the
+    counted rows are written.  No host wait; the words do not depend on the order of the faces."""
+    from .ops import _workspace
+    vertices, faces = _finish_args(vertices, faces, counts, "smooth_mesh")
+    steps = int(steps)
+    if not 0 <= steps <= MAX_SMOOTH_STEPS:
+        raise SfmHipError(f"smooth_mesh: steps {steps} must be in 0..{MAX_SMOOTH_STEPS}")
+    nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    if out is None:
+        out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (nv, 3) or not out.is_contiguous() or out.device != dev:
+        raise SfmHipError("smooth_mesh: out must be a contiguous [m, 3] float32 tensor on the vertices' device")
+    factors = np.ascontiguousarray(np.tile(np.array([lam, mu], np.float32), steps))
+    org = _origin(origin)
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_mesh_smooth_ws_bytes(nv, nf))
+    with on_device(dev):
+        check(L.sfm_mesh_smooth(ptr(vertices) if nv else None, ptr(faces) if nf else None, nv, nf, ptr(counts), 2 * steps,
+                                factors.ctypes.data if steps else None, org.ctypes.data, smooth_scale(extent), ptr(out) if nv else None,
+                                ptr(ws), ws.numel(), stream_ptr()), "sfm_mesh_smooth")
+    return out
+
+
 def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOXELS, w_min=W_MIN, tau=0.01, min_consistent=2, nsrc=4,
-             pad=0.05, clean=False, min_component_share=MIN_COMPONENT_SHARE, min_component_faces=None, largest_only=False):
+             pad=0.05, clean=False, min_component_share=MIN_COMPONENT_SHARE, min_component_faces=None, largest_only=False, normals=False,
+             smooth=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU):
     """A coloured triangle mesh of a registered sequence from run_mvs's depth maps.
 
     images:  the BGR uint8 frames run_mvs got (device tensors or host arrays, K's resolution, posearr's camera order)
@@ -233,6 +315,9 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     clean=True: then the connected components with fewer than `min_component_faces` faces are dropped (clean_mesh; None:
     max(1, floor(min_component_share * faces)); largest_only: all but the largest), and the dict gains `components` and
     `components_kept`.
+    smooth > 0: then that many Taubin pairs (smooth_mesh with `smooth_lambda`, `smooth_mu`, the volume's origin and its longest
+    side as the frame) move the vertices; normals=True: then the dict gains `normals` (m, 3) float64, the vertex normals of the
+    final surface (mesh_normals).  Both are off by default (docs/mesh.md §8) and add no host wait.
     Returns dict(vertices (m, 3) float64, colors (m, 3) float64 B G R, faces (k, 3) int32) for pipeline.to_ply_mesh.
     Two host waits per call: the mesh totals and the one download; every upload is stream-ordered (pinned memory).  (Should the
     downloaded labelling status say "not converged" the labelling is continued, and cleaned and downloaded again, until it has.)"""
@@ -246,6 +331,12 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     if n < 2:
         raise SfmHipError("run_mesh: needs at least two registered views")
     origin, voxel, dims = volume_bounds(mvs_out["points"], resolution, pad)
+    finish = None
+    if int(smooth) != 0 or normals:
+        if not 0 <= int(smooth) <= MAX_SMOOTH_STEPS:
+            raise SfmHipError(f"run_mesh: smooth {smooth} must be in 0..{MAX_SMOOTH_STEPS} pairs")
+        finish = dict(steps=int(smooth), lam=float(smooth_lambda), mu=float(smooth_mu), normals=bool(normals), origin=origin,
+                      extent=voxel * (max(dims) - 1))
     dev = depths[0].device
     require_cuda(*depths)
     if all(torch.is_tensor(im) and im.is_cuda for im in images):
@@ -271,16 +362,44 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
                                  masks=masks, bgr=frames)
         verts, cols, faces, buf = extract_mesh(S, W, C, origin, voxel, w_min, packed=True)
         if clean:
-            return _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only)
+            return _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish)
+        if finish is not None:
+            buf = torch.cat([buf] + _finish(verts, faces, None, finish))
         host = buf.cpu().numpy()                                    # the one download
     nv, nt = len(verts), len(faces)
     fl = host[:6 * nv].view(np.float32)
-    return dict(vertices=fl[:3 * nv].reshape(nv, 3).astype(np.float64), colors=fl[3 * nv:].reshape(nv, 3).astype(np.float64),
-                faces=np.ascontiguousarray(host[6 * nv:].reshape(nt, 3)))
+    out = dict(vertices=fl[:3 * nv].reshape(nv, 3).astype(np.float64), colors=fl[3 * nv:].reshape(nv, 3).astype(np.float64),
+               faces=np.ascontiguousarray(host[6 * nv:6 * nv + 3 * nt].reshape(nt, 3)))
+    if finish is not None:
+        out.update(_finished_rows(host[6 * nv + 3 * nt:], nv, nv, finish))
+    return out
 
 
-def _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only):
-    """run_mesh's tail with clean=True: the cleaned mesh in one download."""
+def _finish(verts, faces, counts, finish):
+    """The finishing steps run_mesh asked for, enqueued: the flat int32 views of the smoothed vertices (when smoothing) and of the
+    normals (when asked), each of the vertices' full size, to be appended to the buffer that is downloaded."""
+    extra = []
+    if finish["steps"]:
+        verts = smooth_mesh(verts, faces, finish["steps"], finish["origin"], finish["extent"], finish["lam"], finish["mu"], counts)
+        extra.append(verts.view(torch.int32).reshape(-1))
+    if finish["normals"]:
+        extra.append(mesh_normals(verts, faces, counts).view(torch.int32).reshape(-1))
+    return extra
+
+
+def _finished_rows(tail, cap, nv, finish):
+    """What _finish appended, sliced from the downloaded words: dict(vertices?, normals?) with the first nv of the cap rows each."""
+    out, fl = {}, tail.view(np.float32)
+    if finish["steps"]:
+        out["vertices"] = fl[:3 * nv].reshape(nv, 3).astype(np.float64)
+        fl = fl[3 * cap:]
+    if finish["normals"]:
+        out["normals"] = fl[:3 * nv].reshape(nv, 3).astype(np.float64)
+    return out
+
+
+def _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish=None):
+    """run_mesh's tail with clean=True: the cleaned mesh (smoothed, with normals: `finish`) in one download."""
     nv, nt = len(verts), len(faces)
     if min_component_faces is None:
         if not (0.0 <= float(min_component_share) <= 1.0):
@@ -292,11 +411,16 @@ def _clean_and_download(verts, cols, faces, min_component_share, min_component_f
             raise SfmHipError(f"run_mesh: min_component_faces {min_faces} is negative")
     labels = None
     while True:
-        *_, labels, buf = clean_mesh(verts, cols, faces, min_faces, largest_only, packed=True, labels=labels)
+        ov, _, of, counts, _, labels, buf = clean_mesh(verts, cols, faces, min_faces, largest_only, packed=True, labels=labels)
+        if finish is not None:                                      # on the counted rows, the counts read on the device
+            buf = torch.cat([buf] + _finish(ov, of, counts, finish))
         host = buf.cpu().numpy()                                    # the one download
         if host[4]:                                                 # converged; otherwise every batch of rounds lowers a label
             break
     kv, kf, ncomp, nkept = (int(v) for v in host[:4])
     fl = host[6:6 + 6 * nv].view(np.float32)
-    return dict(vertices=fl[:3 * kv].reshape(kv, 3).astype(np.float64), colors=fl[3 * nv:3 * (nv + kv)].reshape(kv, 3).astype(np.float64),
-                faces=np.ascontiguousarray(host[6 + 6 * nv:6 + 6 * nv + 3 * kf].reshape(kf, 3)), components=ncomp, components_kept=nkept)
+    out = dict(vertices=fl[:3 * kv].reshape(kv, 3).astype(np.float64), colors=fl[3 * nv:3 * (nv + kv)].reshape(kv, 3).astype(np.float64),
+               faces=np.ascontiguousarray(host[6 + 6 * nv:6 + 6 * nv + 3 * kf].reshape(kf, 3)), components=ncomp, components_kept=nkept)
+    if finish is not None:
+        out.update(_finished_rows(host[6 + 6 * nv + 3 * nt:], nv, kv, finish))
+    return out

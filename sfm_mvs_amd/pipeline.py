@@ -639,11 +639,12 @@ def to_ply(path, point_cloud, colors, densify=False):
     return len(verts)
 
 
-def to_ply_mesh(path, vertices, colors, faces):
+def to_ply_mesh(path, vertices, colors, faces, normals=None):
     """Point_Cloud/dense_mesh.ply: the surface of mesh.run_mesh in to_ply's units and columns (x200, B G R uchar, so that it
     overlays sparse.ply and dense.ply), colours rounded as floor(c + 0.5) clamped to 0..255, plus `element face k` with
     `property list uchar int vertex_indices`.  No centroid outlier cut: it would leave faces pointing at dropped vertices.
-    Returns (vertices, faces) written."""
+    normals ((m, 3), mesh.run_mesh(normals=True)): written unscaled as `property float nx`, `ny`, `nz` after `z`; without them the
+    file is what it always was.  Returns (vertices, faces) written."""
     verts = np.asarray(vertices, np.float64).reshape(-1, 3) * 200
     cols = np.clip(np.floor(np.asarray(colors, np.float64).reshape(-1, 3) + 0.5), 0, 255).astype(np.int64)
     tris = np.asarray(faces).reshape(-1, 3).astype(np.int64)
@@ -651,12 +652,20 @@ def to_ply_mesh(path, vertices, colors, faces):
         raise ValueError(f"to_ply_mesh: {len(verts)} vertices but {len(cols)} colours")
     if len(tris) and (tris.min() < 0 or tris.max() >= len(verts)):
         raise ValueError("to_ply_mesh: a face names a vertex that does not exist")
-    lines = ["ply", "format ascii 1.0", "element vertex %d" % len(verts), "property float x", "property float y", "property float z",
-             "property uchar blue", "property uchar green", "property uchar red", "element face %d" % len(tris),
+    if normals is not None:
+        nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+        if len(nrm) != len(verts):
+            raise ValueError(f"to_ply_mesh: {len(verts)} vertices but {len(nrm)} normals")
+    lines = ["ply", "format ascii 1.0", "element vertex %d" % len(verts), "property float x", "property float y", "property float z"]
+    if normals is not None:
+        lines += ["property float nx", "property float ny", "property float nz"]
+    lines += ["property uchar blue", "property uchar green", "property uchar red", "element face %d" % len(tris),
              "property list uchar int vertex_indices", "end_header"]
     with open(path + "/Point_Cloud/dense_mesh.ply", "w") as f:
         f.write("\n".join(lines) + "\n")
-        if len(verts):
+        if len(verts) and normals is not None:
+            np.savetxt(f, np.hstack([verts, nrm, cols]), "%f %f %f %f %f %f %d %d %d")
+        elif len(verts):
             np.savetxt(f, np.hstack([verts, cols]), "%f %f %f %d %d %d")
         if len(tris):
             np.savetxt(f, np.hstack([np.full((len(tris), 1), 3), tris]), "%d %d %d %d")
