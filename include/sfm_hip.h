@@ -812,6 +812,11 @@ int sfm_debug_knn_prep_general(int on);
  * derives from the batch size (256 up to four pairs, then as many as fill one resident round: 128 for eight); 0 restores the rule.
  * Results do not depend on it (tests/test_gpu_knn_prep_blocks.py); it also serves same-box timing comparisons. */
 int sfm_debug_knn_prep_blocks(int n);
+/* Test hook: with on == 0 every following knn_refine_kernel launch runs the quantised body's integer row passes per query (two
+ * 8-row records of each of a wave's four queries per pass, trip count of the longest list) instead of pooling the wave's four record
+ * lists over its eight 8-lane groups (the default, on != 0).  Results do not depend on it (tests/test_gpu_knn_refine_pooled.py); it
+ * also serves same-box timing comparisons. */
+int sfm_debug_knn_refine_pooled(int on);
 int sfm_profile_read(int slot, double* total_ms_host, int64_t* launches_host);
 /* How often library calls of this process have WAITED for the device so far (cumulative; the RANSAC entry points read the
  * hypothesis scores back chunk by chunk, the Schur solver its convergence scalars).  Diagnostics: bench.py reports the

@@ -115,6 +115,7 @@ SIGNATURES = {
     "sfm_debug_set_trace": (_int, [_vp]),
     "sfm_debug_knn_split_delay": (_int, [_int, _int]),
     "sfm_debug_knn_prep_general": (_int, [_int]),
+    "sfm_debug_knn_refine_pooled": (_int, [_int]),
     "sfm_debug_knn_prep_blocks": (_int, [_int]),
     "sfm_profile_read": (_int, [_int, _c.POINTER(_f64), _c.POINTER(_i64)]),
 }

@@ -3016,7 +3016,7 @@ __device__ __forceinline__ void refine_q8_body(
     const float* __restrict__ qerr, const int* __restrict__ keys, const int* __restrict__ sttab, int64_t s_keys, int nstr, const int* __restrict__ rb_last8,
     int n_rb1, int G8, double ratio, int* __restrict__ ratio_counts, float* __restrict__ qrows /*LDS [kRefQ][128]*/,
     unsigned char* __restrict__ qb /*LDS [kRefQ][128]*/, int* __restrict__ recl /*LDS [kRefQ][2 * kRecCapI8]*/, int* __restrict__ quall /*LDS [kRefQ][kQualCap]*/,
-    long long* __restrict__ trace) {
+    long long* __restrict__ trace, int pooled /*0: test hook (sfm_debug_knn_refine_pooled), the per-query row passes*/) {
     const int n_wg = (nq + kRefQ - 1) / kRefQ, n_tot = B * n_wg, wg_chunk = (n_tot + 7) >> 3;
     const int bidt = n_tot >= 64 ? (int)(blockIdx.x & 7) * wg_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (bidt >= n_tot) return;
@@ -3199,6 +3199,54 @@ __device__ __forceinline__ void refine_q8_body(
         __builtin_amdgcn_wave_barrier();
         nrec = 0;
     };
+    // The same evaluation with the wave's four record lists POOLED: process() runs max(nrec) / 2 passes and the lanes of the three
+    // shorter lists idle through most of them; here pooled record r = 8 pass + (lane >> 3) belongs to the query whose prefix range
+    // holds it, so the wave runs ceil(sum(nrec) / 8) passes.  The four counts, their prefixes and the four row-list lengths live in
+    // scalar registers; a lane finds its owner with three compares.  The owners of a pass occupy ascending lane ranges, so an
+    // owner's share of the ballot is the ballot below its range's end minus the ballot below its start (scalar popcounts).  Same
+    // records, same rows, same test (D <= dlim as w + 2 dot <= dlim - cq, no overflow: |cq| < 2^24, dlim < 2^24 or INT_MAX): the row
+    // lists hold today's rows in another order, which Best2's (distance, index) order with unique insertion does not see.
+    auto process_pooled = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int p1 = __builtin_amdgcn_readlane(nrec, 0), p2 = p1 + __builtin_amdgcn_readlane(nrec, 16),
+                  p3 = p2 + __builtin_amdgcn_readlane(nrec, 32), p4 = p3 + __builtin_amdgcn_readlane(nrec, 48);
+        int n0 = __builtin_amdgcn_readlane(nqual, 0), n1 = __builtin_amdgcn_readlane(nqual, 16), n2 = __builtin_amdgcn_readlane(nqual, 32),
+            n3 = __builtin_amdgcn_readlane(nqual, 48);
+        const int dl = dlim == INT_MAX ? INT_MAX : dlim - cq;    // (per query; the owner's is selected below)
+        const int l0 = __builtin_amdgcn_readlane(dl, 0), l1 = __builtin_amdgcn_readlane(dl, 16), l2 = __builtin_amdgcn_readlane(dl, 32),
+                  l3 = __builtin_amdgcn_readlane(dl, 48);
+        auto below = [](int x) -> unsigned long long { return x <= 0 ? 0ull : x >= 64 ? ~0ull : (1ull << x) - 1ull; };   // lanes < x
+#pragma unroll 1
+        for (int r0 = 0; r0 < p4; r0 += 8) {
+            if (max(max(n0, n1), max(n2, n3)) > kQualCap - 64) {   // (a pass can give all its 64 rows to one owner)
+                nqual = sub == 0 ? n0 : sub == 1 ? n1 : sub == 2 ? n2 : n3;
+                eval_list();
+                n0 = n1 = n2 = n3 = 0;
+            }
+            const int r = r0 + (lane >> 3);
+            const bool o1 = r >= p1, o2 = r >= p2, o3 = r >= p3, live = r < p4;
+            auto own = [&](int x0, int x1, int x2, int x3) { return o3 ? x3 : o2 ? x2 : o1 ? x1 : x0; };
+            const int slot = wave * 4 + own(0, 1, 2, 3);
+            const int* __restrict__ rp = recl + slot * (2 * kRecCapI8) + 2 * (r - own(0, p1, p2, p3));
+            const int key = live ? rp[0] : 0, inf = live ? rp[1] : 0;                          // (idle lanes: tile 0, result unused)
+            int row;
+            const int D = int_row(min(inf >> 1, tiles - 1), inf & 1, key & 1, lane & 7, slot, 0, row);
+            const bool take = live && row < nt && D <= own(l0, l1, l2, l3);
+            const unsigned long long tm = __ballot(take);
+            const int c1 = __popcll(tm & below(8 * (p1 - r0))), c2 = __popcll(tm & below(8 * (p2 - r0))), c3 = __popcll(tm & below(8 * (p3 - r0))),
+                      c4 = __popcll(tm);
+            if (take) quall[slot * kQualCap + own(n0, n1 - c1, n2 - c2, n3 - c3) +
+                            (int)__builtin_amdgcn_mbcnt_hi((unsigned)(tm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)tm, 0u))] = row;
+            n0 += c1; n1 += c2 - c1; n2 += c3 - c2; n3 += c4 - c3;
+        }
+        __builtin_amdgcn_wave_barrier();
+        nqual = sub == 0 ? n0 : sub == 1 ? n1 : sub == 2 ? n2 : n3;
+        nrec = 0;
+    };
+    // (the two mid-list flushes below — a query lists more than kRecCapI8 - 16 records: cold — keep process(): with a pooled copy
+    // at each of them the kernel no longer fits 128 VGPRs without scratch)
+    auto process_any = [&]() { if (pooled) process_pooled(); else process(); };
     {   // the chunks still in registers: one prefix sum when the list holds them all
         bool take[kS1];
         int mine = 0;
@@ -3245,7 +3293,7 @@ __device__ __forceinline__ void refine_q8_body(
         }
     }
     if (trace && threadIdx.x == 0) { trace[16 * bidt + 2] = wall_clock64(); trace[16 * bidt + 13] = nrec; }
-    process();
+    process_any();
     if (trace && threadIdx.x == 0) { trace[16 * bidt + 3] = wall_clock64(); trace[16 * bidt + 14] = nqual; }
     eval_list();
     if (trace && threadIdx.x == 0) trace[16 * bidt + 4] = wall_clock64();
@@ -3362,7 +3410,7 @@ __global__ __launch_bounds__(256, 4) void knn_refine_kernel(
     // the exact-integer body (qi8 == null: not planned)
     const unsigned char* __restrict__ qi8, const unsigned char* __restrict__ ti8, int64_t s_qi8, int64_t s_ti8, const int* __restrict__ wq8,
     const int* __restrict__ wt8, const int* __restrict__ keys8, const int* __restrict__ sttab8, int64_t s_keys8, int nstr8,
-    const int* __restrict__ rb_last8, int n_rb1_8, int G8) {
+    const int* __restrict__ rb_last8, int n_rb1_8, int G8, int refine_pooled) {
     // XCD-aware order (see the filter): physical workgroup b takes query block (b % 8) * chunk + b / 8, so the queries an
     // XCD refines are (roughly) those whose candidate records its own filter workgroups wrote.  Batched: the query
     // blocks of all pairs form one sequence, pair after pair.
@@ -3398,7 +3446,7 @@ __global__ __launch_bounds__(256, 4) void knn_refine_kernel(
     if constexpr (FRAG)
     if (qi8 && minfo && minfo[kMinfoI8] && minfo[kMinfoQ8]) {   // (uniform) the integer body ran on quantised float data
         refine_q8_body(P, B, ldq, nq, ldt, nt, tiles, minfo, qi8, ti8, s_qi8, s_ti8, wq8, wt8, s_qn, s_tn, qerr, keys8, sttab8, s_keys8, nstr8, rb_last8, n_rb1_8, G8,
-                       ratio, ratio_counts, &qrows[0][0], reinterpret_cast<unsigned char*>(&qhalf[0][0]), &rec[0][0], &qual[0][0], trace);
+                       ratio, ratio_counts, &qrows[0][0], reinterpret_cast<unsigned char*>(&qhalf[0][0]), &rec[0][0], &qual[0][0], trace, refine_pooled);
         return;
     }
     if constexpr (FRAG)
@@ -4047,6 +4095,7 @@ long long* g_trace = nullptr;   // dev diagnostics only
 int g_split_delay_wg = -1;      // test hook: see knn_split_images_kernel
 long long g_split_delay_ticks = 0;
 int g_prep_general = 0;         // test hook: quantised pairs take the general row loop of knn_prep_kernel
+int g_refine_pooled = 1;       // test hook: 0 sends refine_q8_body through the per-query row passes instead of the pooled ones
 int g_prep_blocks = 0;          // test hook: row workgroups per pair of knn_prep_kernel (0: prep_blocks' rule)
 
 // Row workgroups per pair of the prep launch.  Every workgroup pays a fixed part — the quantisation sample, the prologue, the
@@ -4349,6 +4398,11 @@ extern "C" int sfm_debug_knn_prep_blocks(int n) {
     return SFM_OK;
 }
 
+extern "C" int sfm_debug_knn_refine_pooled(int on) {
+    g_refine_pooled = on != 0;
+    return SFM_OK;
+}
+
 extern "C" int sfm_debug_set_trace(void* dev_buf) {
     g_trace = static_cast<long long*>(dev_buf);
     return SFM_OK;
@@ -4500,7 +4554,8 @@ int knn_batch_impl(int B, const BatchPtrs& P, int64_t nq, int64_t ldq, int64_t n
                        w.cand_i, p.rows_per_block, p.tiles, p.units, p.G, p.smax * p.nsub, p.nsub, force_mode, w.midflag, w.bmax,               \
                        p.split ? w.minfo : nullptr, p.split ? w.qerr : nullptr, w.s_qn, THALF, w.tn, w.wg_begin, w.rb_first, w.rb_last, p.n_rb1, \
                        w.s_cand, S_THALF, w.s_tn, ratio, ratio_counts, ratio_stride, chain_scale, p.q4 ? 1 : 0, g_trace ? g_trace + 16384 : nullptr,    \
-                       w.qi8, w.ti8, w.s_qi8, w.s_ti8, w.wq, w.wt, w.keys8, w.sttab8, w.s_keys8, nstr8, w.rb_last8, p8.n_rb1, p8.G)
+                       w.qi8, w.ti8, w.s_qi8, w.s_ti8, w.wq, w.wt, w.keys8, w.sttab8, w.s_keys8, nstr8, w.rb_last8, p8.n_rb1, p8.G,    \
+                       g_refine_pooled)
     if (p.q4) SFM_LAUNCH_REFINE(true, reinterpret_cast<const unsigned short*>(w.tfrag), w.s_tfrag / 2);      // (stride in 16-bit elements)
     else SFM_LAUNCH_REFINE(false, p.split ? w.tsplit + (size_t)2 * p.tiles * kTileT * kDim : nullptr, w.s_tsplit);
 #undef SFM_LAUNCH_REFINE
