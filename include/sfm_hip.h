@@ -785,6 +785,56 @@ int sfm_mesh_smooth(const float* vertices_dev, const int32_t* faces_dev, int64_t
                     size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MESH-DECIMATE (no reference counterpart; csrc/mesh_decimate.hip, docs/mesh.md §9): simplification of a triangle mesh by vertex
+ * clustering, after sfm_mesh_extract, sfm_mesh_clean or sfm_mesh_smooth: the vertices of one cell of a regular grid become one
+ * vertex at their mean, the faces are renumbered, and the faces that lose a corner go.  This is open3d's
+ * simplify_vertex_clustering with average contraction and its rotation-normalised triangle set, made order-exact: every sum is an
+ * int64 sum of quantised terms and every choice is a minimum, so no result depends on the order in which atomics land; every float32
+ * and float64 operation is correctly rounded in the order written here (no FMA, no reassociation); int64 -> float64 rounds to
+ * nearest even.  tests/np_mesh_decimate.py restates every output bit for bit.
+ *
+ *   input       vertices_dev [nv_cap][3] float32, optional colors_dev [nv_cap][3] float32, faces_dev [nf_cap][3] int32;
+ *               0 <= nv_cap, nf_cap <= 2^31 - 1
+ *   counts_dev  optional int32[2] = (nv, nf), READ ON THE DEVICE, exactly as in MESH-FINISH (the first two words of sfm_mesh_clean's
+ *               counts are this pair).  NULL: the capacities.  A count that is negative or above its capacity is taken as the capacity.
+ *   frame       origin_host float32 [3] = o (finite), cell > 0 (finite), dims_host int32 [3] = (dims_x, dims_y, dims_z), each >= 1,
+ *               dims_x * dims_y * dims_z <= 2^27; pscale > 0 (finite; the wrapper passes MESH-FINISH's power of two).
+ *   cell of a vertex   per coordinate t_c = floor(((double)p_c - (double)o_c) / (double)cell).  The vertex is USABLE iff for all
+ *               three c:  t_c >= 0 && t_c < dims_c, tested in float64 before any conversion to an integer (NaN and +-inf fail), and
+ *               r_c = rintf((p_c - o_c) * pscale) has |r_c| <= 2^30 (MESH-FINISH's quantisation; NaN fails).
+ *               key = (t_z * dims_y + t_y) * dims_x + t_x  (< 2^27).
+ *   leader      leader(key) = the smallest usable vertex id of the cell among the first nv.
+ *   new vertices   the leaders in ascending id order; the new id of a leader is its rank among the leaders, and the new id of every
+ *               usable vertex is that of its cell's leader.  With acc_c = the int64 sum of r_c over the usable members of the cell
+ *               and cnt = their number:  p'_c = (float)(((double)acc_c / (double)cnt) / (double)pscale + (double)o_c).
+ *               Colours, when given: per component the term of a member is (int64) rintf(c * 65536.0f) if fabsf(c) <= 32768.0f (NaN
+ *               fails), else 0; the member counts in cnt either way;  c' = (float)(((double)acc / (double)cnt) / 65536.0).
+ *               (|r| <= 2^30, terms <= 2^31, at most 2^31 members: every sum stays below 2^63.)
+ *   faces       of the first nf, a face is VALID iff its three indices lie in 0..nv-1 (no other index is dereferenced), and a valid
+ *               face is LIVE iff its three corners are usable and their three new ids are pairwise different.  The live faces are
+ *               output in their input order as (a', b', c') in the input corner order: winding is kept.
+ *   dedupe == 1 two live faces are EQUAL iff their new triples are equal after rotating each so that its smallest id comes first (a
+ *               face and its flipped twin are not equal).  Of equal faces only the one with the lowest input index is output.
+ *               dedupe == 0 outputs every live face.
+ *   output      out_vertices_dev, out_colors_dev (iff colors_dev), out_faces_dev: buffers of the input capacities, distinct from
+ *               the inputs; nothing is written at or past the counted rows.  out_counts_dev int32[4] = (vertices out, faces out,
+ *               unusable vertices among the first nv, live faces dropped as duplicates); its first two words are what
+ *               sfm_mesh_normals reads as counts_dev, so normals follow on the stream with no host wait.
+ * Errors (SFM_ERR_ARG, before any device call): a capacity negative or above 2^31 - 1; a dim < 1 or a product above 2^27; cell or
+ *   pscale not finite or not positive; an origin coordinate that is not finite; dedupe not 0 or 1; NULL where a capacity is non-zero
+ *   (vertices in and out with nv_cap, faces in and out with nf_cap; origin_host, dims_host, out_counts_dev and the workspace
+ *   always); colours in without colours out or the reverse; an output pointer equal to an input pointer; a workspace smaller than
+ *   the _ws_bytes twin says.
+ * The _ws_bytes twin returns 0 for invalid sizes (76 bytes per vertex, 4 per cell, 1 per face and 4 per slot of the face set: the
+ *   smallest power of two >= 2 * nf_cap).
+ * ---------------------------------------------------------------------- */
+size_t sfm_mesh_decimate_ws_bytes(int64_t nv_cap, int64_t nf_cap, const int32_t dims[3]);
+int sfm_mesh_decimate(const float* vertices_dev, const float* colors_dev, const int32_t* faces_dev, int64_t nv_cap, int64_t nf_cap,
+                      const int32_t* counts_dev, const float* origin_host, float cell, const int32_t* dims_host, float pscale, int dedupe,
+                      float* out_vertices_dev, float* out_colors_dev, int32_t* out_faces_dev, int32_t* out_counts_dev, void* ws_dev,
+                      size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets
  * its dominant kernels with hipEvents recorded on the launch stream.
  * sfm_profile_read synchronises those events, returns the summed device time

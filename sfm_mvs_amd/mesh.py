@@ -6,7 +6,8 @@ tensors in, device tensors out, stream ordered, no CPU path.  The host part is t
 (float64) and the cast of the cameras' projection matrices.  docs/mesh.md describes the algorithm and its numbers.
 Opt-in after the extraction: `mesh_components` / `clean_mesh` (sfm_mesh_components, sfm_mesh_clean; "MESH-CLEAN") drop the small
 connected components, `run_mesh(clean=True)` (docs/mesh.md §7); `smooth_mesh` / `mesh_normals` (sfm_mesh_smooth, sfm_mesh_normals;
-"MESH-FINISH") smooth the surface and give it vertex normals, `run_mesh(smooth=..., normals=True)` (docs/mesh.md §8).
+"MESH-FINISH") smooth the surface and give it vertex normals, `run_mesh(smooth=..., normals=True)` (docs/mesh.md §8);
+`decimate_mesh` (sfm_mesh_decimate; "MESH-DECIMATE") simplifies it by vertex clustering, `run_mesh(decimate=...)` (docs/mesh.md §9).
 """
 import numpy as np
 import torch
@@ -30,6 +31,10 @@ MIN_COMPONENT_SHARE = 1.0 / 512 # run_mesh(clean=True) drops components with few
 SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53   # Taubin's pair: the pass band ends at 1/lambda + 1/mu = 0.113
 MAX_SMOOTH_STEPS = 32           # pairs: sfm_mesh_smooth takes 64 steps
 SMOOTH_PAIRS = 10               # the pair count the calibration recommends (docs/mesh.md §8); run_mesh's own default stays 0
+
+# Decimation (include/sfm_hip.h, "MESH-DECIMATE"; docs/mesh.md §9).
+MAX_CELLS = 1 << 27             # cells per clustering grid
+DECIMATE_CELLS = 2.0            # the cell size in voxels the calibration recommends (docs/mesh.md §9); run_mesh's own default stays 0
 
 
 def volume_bounds(points, resolution=256, pad=0.05):
@@ -302,9 +307,66 @@ def smooth_mesh(vertices, faces, steps, origin, extent, lam=SMOOTH_LAMBDA, mu=SM
     return out
 
 
+def decimate_mesh(vertices, colors, faces, origin, cell, dims, extent, dedupe=True, counts=None, packed=False):
+    """Vertex clustering (sfm_mesh_decimate): the vertices of one cell of the grid (`origin` (3,) its corner, `cell` the cell's
+    side, `dims` (nx, ny, nz) cells, at most 2^27) become one vertex at the mean of their positions (quantised as in smooth_mesh,
+    `extent` the frame's longest side) and of their colours; faces are renumbered, the ones left with fewer than three different
+    corners are dropped, and with `dedupe` so are all but the first of the faces that became equal up to a rotation.  A vertex
+    outside the grid, or not finite, is unusable: it and its faces go.  vertices [m, 3] float32, colors [m, 3] float32 or None,
+    faces [k, 3] int32 device tensors; counts as in mesh_normals.
+    Returns (vertices, colors or None, faces, counts): tensors of the INPUT sizes of which the first counts[0] / counts[1] rows are
+    the result and the rest is not written; counts an int32 [4] device tensor (vertices out, faces out, unusable vertices, live
+    faces dropped as duplicates) whose first two words mesh_normals takes as its counts.  No host wait; the words do not depend
+    on the order in which anything lands.
+    packed=True: returns (vertices, colors, faces, counts, buf) with buf the one int32 buffer that holds counts [4], vertices,
+    colours and faces in that order, so that a caller downloads once and slices on the host."""
+    from .ops import _workspace
+    vertices, faces = _finish_args(vertices, faces, counts, "decimate_mesh")
+    require_cuda(colors)
+    if colors is not None and (colors.dtype != torch.float32 or colors.shape != vertices.shape or colors.device != vertices.device):
+        raise SfmHipError("decimate_mesh: colors must be [m, 3] float32 like the vertices")
+    colors = None if colors is None else colors.contiguous()
+    d = np.ascontiguousarray(np.asarray(dims, np.int64).reshape(3))
+    if np.any(d < 1) or int(d[0]) * int(d[1]) * int(d[2]) > MAX_CELLS:
+        raise SfmHipError(f"decimate_mesh: {d[0]} x {d[1]} x {d[2]} cells: each must be >= 1 and the product <= 2^27")
+    d = np.ascontiguousarray(d.astype(np.int32))
+    nv, nf, dev = int(vertices.shape[0]), int(faces.shape[0]), vertices.device
+    ncol = nv if colors is not None else 0
+    buf = torch.empty(4 + 3 * nv + 3 * ncol + 3 * nf, dtype=torch.int32, device=dev)
+    out_n = buf[:4]
+    out_v = buf[4:4 + 3 * nv].view(torch.float32).view(nv, 3)
+    out_c = buf[4 + 3 * nv:4 + 3 * (nv + ncol)].view(torch.float32).view(ncol, 3) if colors is not None else None
+    out_f = buf[4 + 3 * (nv + ncol):].view(nf, 3)
+    org = _origin(origin)
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_mesh_decimate_ws_bytes(nv, nf, d.ctypes.data))
+    with on_device(dev):
+        check(L.sfm_mesh_decimate(ptr(vertices) if nv else None, ptr(colors) if ncol else None, ptr(faces) if nf else None, nv, nf,
+                                  ptr(counts), org.ctypes.data, float(cell), d.ctypes.data, smooth_scale(extent), int(bool(dedupe)),
+                                  ptr(out_v) if nv else None, ptr(out_c) if ncol else None, ptr(out_f) if nf else None, ptr(out_n),
+                                  ptr(ws), ws.numel(), stream_ptr()), "sfm_mesh_decimate")
+    return (out_v, out_c, out_f, out_n, buf) if packed else (out_v, out_c, out_f, out_n)
+
+
+def decimate_frame(origin, voxel, dims, decimate):
+    """run_mesh's clustering grid for a volume (origin (3,) float64, voxel, dims) and a cell of `decimate` voxels: (origin float64
+    (3,), cell, dims, extent).  The grid starts one cell below the volume's origin and has floor((dims_c - 1) * voxel / cell) + 3
+    cells per axis, so that vertices smoothing pushed slightly outside the volume stay usable; extent, the side the quantisation
+    is scaled to, is the longest side of this padded grid.  Raises SfmHipError when `decimate` is not a finite number >= 1 or the
+    grid exceeds 2^27 cells."""
+    decimate = float(decimate)
+    if not (np.isfinite(decimate) and decimate >= 1.0):
+        raise SfmHipError(f"run_mesh: decimate {decimate} must be 0 (off) or a finite cell size >= 1 voxel")
+    cell = decimate * float(voxel)
+    cells = tuple(int(np.floor((int(n) - 1) * float(voxel) / cell)) + 3 for n in dims)
+    if int(np.prod(cells, dtype=np.int64)) > MAX_CELLS:
+        raise SfmHipError(f"run_mesh: the decimation grid {cells[0]} x {cells[1]} x {cells[2]} exceeds 2^27 cells; raise decimate")
+    return np.asarray(origin, np.float64).reshape(3) - cell, cell, cells, cell * max(cells)
+
+
 def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOXELS, w_min=W_MIN, tau=0.01, min_consistent=2, nsrc=4,
              pad=0.05, clean=False, min_component_share=MIN_COMPONENT_SHARE, min_component_faces=None, largest_only=False, normals=False,
-             smooth=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU):
+             smooth=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, decimate=0, decimate_dedupe=True):
     """A coloured triangle mesh of a registered sequence from run_mvs's depth maps.
 
     images:  the BGR uint8 frames run_mvs got (device tensors or host arrays, K's resolution, posearr's camera order)
@@ -318,6 +380,11 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     smooth > 0: then that many Taubin pairs (smooth_mesh with `smooth_lambda`, `smooth_mu`, the volume's origin and its longest
     side as the frame) move the vertices; normals=True: then the dict gains `normals` (m, 3) float64, the vertex normals of the
     final surface (mesh_normals).  Both are off by default (docs/mesh.md §8) and add no host wait.
+    decimate > 0: then, after the clean-up and the smoothing and before the normals, the vertices of every cell of `decimate`
+    (>= 1, a float) voxels become one (decimate_mesh over decimate_frame's grid; `decimate_dedupe`: faces that became equal are
+    output once); vertices, colors, faces and normals then describe the decimated mesh, and the dict gains `decimated_from`
+    (vertices, faces) before the step and `decimate_unusable`, the vertices that fell outside the grid.  Off by default
+    (DECIMATE_CELLS is the recommended cell, docs/mesh.md §9); no host wait is added and the rows before the step are not downloaded.
     Returns dict(vertices (m, 3) float64, colors (m, 3) float64 B G R, faces (k, 3) int32) for pipeline.to_ply_mesh.
     Two host waits per call: the mesh totals and the one download; every upload is stream-ordered (pinned memory).  (Should the
     downloaded labelling status say "not converged" the labelling is continued, and cleaned and downloaded again, until it has.)"""
@@ -337,6 +404,9 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
             raise SfmHipError(f"run_mesh: smooth {smooth} must be in 0..{MAX_SMOOTH_STEPS} pairs")
         finish = dict(steps=int(smooth), lam=float(smooth_lambda), mu=float(smooth_mu), normals=bool(normals), origin=origin,
                       extent=voxel * (max(dims) - 1))
+    dec = None
+    if decimate != 0:
+        dec = dict(frame=decimate_frame(origin, voxel, dims, decimate), dedupe=bool(decimate_dedupe))
     dev = depths[0].device
     require_cuda(*depths)
     if all(torch.is_tensor(im) and im.is_cuda for im in images):
@@ -362,7 +432,11 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
                                  masks=masks, bgr=frames)
         verts, cols, faces, buf = extract_mesh(S, W, C, origin, voxel, w_min, packed=True)
         if clean:
-            return _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish)
+            return _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish, dec)
+        if dec is not None:
+            parts = _decimate(verts, cols, faces, None, finish, dec)
+            host = (torch.cat(parts) if len(parts) > 1 else parts[0]).cpu().numpy()     # the one download
+            return _decimated_rows(host, len(verts), len(faces), (len(verts), len(faces)), finish)
         if finish is not None:
             buf = torch.cat([buf] + _finish(verts, faces, None, finish))
         host = buf.cpu().numpy()                                    # the one download
@@ -398,8 +472,35 @@ def _finished_rows(tail, cap, nv, finish):
     return out
 
 
-def _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish=None):
-    """run_mesh's tail with clean=True: the cleaned mesh (smoothed, with normals: `finish`) in one download."""
+def _decimate(verts, cols, faces, counts, finish, dec):
+    """run_mesh's steps after the clean-up when decimate is on, enqueued: the smoothing (when asked), the clustering, the normals of
+    the decimated surface (when asked, read through the clustering's counts on the device).  Returns the flat int32 tensors to
+    download: decimate_mesh's packed buffer and the normals, each of the input's full size."""
+    if finish is not None and finish["steps"]:
+        verts = smooth_mesh(verts, faces, finish["steps"], finish["origin"], finish["extent"], finish["lam"], finish["mu"], counts)
+    origin, cell, cells, extent = dec["frame"]
+    dv, _, df, dn, buf = decimate_mesh(verts, cols, faces, origin, cell, cells, extent, dec["dedupe"], counts, packed=True)
+    parts = [buf]
+    if finish is not None and finish["normals"]:
+        parts.append(mesh_normals(dv, df, dn).view(torch.int32).reshape(-1))
+    return parts
+
+
+def _decimated_rows(words, nv_cap, nf_cap, before, finish):
+    """What _decimate left, sliced from the downloaded words: run_mesh's dict of the decimated mesh."""
+    kv, kf, unusable = (int(v) for v in words[:3])
+    fl = words[4:4 + 6 * nv_cap].view(np.float32)
+    out = dict(vertices=fl[:3 * kv].reshape(kv, 3).astype(np.float64), colors=fl[3 * nv_cap:3 * (nv_cap + kv)].reshape(kv, 3).astype(np.float64),
+               faces=np.ascontiguousarray(words[4 + 6 * nv_cap:4 + 6 * nv_cap + 3 * kf].reshape(kf, 3)),
+               decimated_from=(int(before[0]), int(before[1])), decimate_unusable=unusable)
+    if finish is not None and finish["normals"]:
+        tail = words[4 + 6 * nv_cap + 3 * nf_cap:].view(np.float32)
+        out["normals"] = tail[:3 * kv].reshape(kv, 3).astype(np.float64)
+    return out
+
+
+def _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish=None, dec=None):
+    """run_mesh's tail with clean=True: the cleaned mesh (smoothed, decimated, with normals: `finish`, `dec`) in one download."""
     nv, nt = len(verts), len(faces)
     if min_component_faces is None:
         if not (0.0 <= float(min_component_share) <= 1.0):
@@ -411,13 +512,19 @@ def _clean_and_download(verts, cols, faces, min_component_share, min_component_f
             raise SfmHipError(f"run_mesh: min_component_faces {min_faces} is negative")
     labels = None
     while True:
-        ov, _, of, counts, _, labels, buf = clean_mesh(verts, cols, faces, min_faces, largest_only, packed=True, labels=labels)
-        if finish is not None:                                      # on the counted rows, the counts read on the device
+        ov, oc, of, counts, _, labels, buf = clean_mesh(verts, cols, faces, min_faces, largest_only, packed=True, labels=labels)
+        if dec is not None:                                         # counts and status, then the decimated mesh alone
+            buf = torch.cat([buf[:6]] + _decimate(ov, oc, of, counts, finish, dec))
+        elif finish is not None:                                    # on the counted rows, the counts read on the device
             buf = torch.cat([buf] + _finish(ov, of, counts, finish))
         host = buf.cpu().numpy()                                    # the one download
         if host[4]:                                                 # converged; otherwise every batch of rounds lowers a label
             break
     kv, kf, ncomp, nkept = (int(v) for v in host[:4])
+    if dec is not None:
+        out = _decimated_rows(host[6:], nv, nt, (kv, kf), finish)
+        out.update(components=ncomp, components_kept=nkept)
+        return out
     fl = host[6:6 + 6 * nv].view(np.float32)
     out = dict(vertices=fl[:3 * kv].reshape(kv, 3).astype(np.float64), colors=fl[3 * nv:3 * (nv + kv)].reshape(kv, 3).astype(np.float64),
                faces=np.ascontiguousarray(host[6 + 6 * nv:6 + 6 * nv + 3 * kf].reshape(kf, 3)), components=ncomp, components_kept=nkept)
