@@ -835,6 +835,78 @@ int sfm_mesh_decimate(const float* vertices_dev, const float* colors_dev, const 
                       size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MESH-TEXTURE (no reference counterpart; csrc/mesh_texture.hip, docs/mesh.md §10): a texture map for a triangle mesh from the
+ * photographs it was built from, after sfm_mesh_extract, sfm_mesh_clean, sfm_mesh_smooth or sfm_mesh_decimate: a depth map of the
+ * mesh in every view (the occlusion test), the view each face is textured from, and an atlas in which every face owns half of a
+ * square cell.  Every result is a minimum or a pure function of its inputs, so nothing depends on the order in which atomics land;
+ * everything is float32 and every operation is correctly rounded in the order written here (no FMA, no reassociation; IEEE `/`,
+ * rintf = to nearest even, floorf, ceilf).  tests/np_mesh_texture.py restates the three outputs bit for bit.
+ *
+ *   input       vertices_dev [nv_cap][3] float32, faces_dev [nf_cap][3] int32; 0 <= nv_cap, nf_cap <= 2^31 - 1
+ *   counts_dev  optional int32[2] = (nv, nf), READ ON THE DEVICE, exactly as in MESH-FINISH and MESH-DECIMATE.  NULL: the
+ *               capacities.  A count that is negative or above its capacity is taken as the capacity.
+ *   valid face  one of the first nf faces whose three indices lie in 0..nv-1; no other index is dereferenced.
+ *   views       P_dev [n][12] float32, row-major 3 x 4 (mesh.projection_rows), 1 <= n <= 65536; frames of w x h pixels,
+ *               w, h >= 2, w * h <= 2^26.
+ *   projection  of a point (x, y, z) in view v, with P = P_dev[v]:  p_r = ((P_r0*x + P_r1*y) + P_r2*z) + P_r3 for r = 0, 1, 2;
+ *               sx = p_0 / p_2,  sy = p_1 / p_2,  depth = p_2.  The point is PROJECTABLE iff p_2 > 0 and sx, sy and p_2 are finite.
+ *               Pixel (x, y) has its centre at (x, y).
+ *   edge function   E_ab(x, y) = (bx - ax)*(y - ay) - (by - ay)*(x - ax) over screen points a, b;  area2 = E_ab(cx, cy).
+ *
+ * sfm_mesh_render_depth — zbuf_dev [n][h][w] float32, written with +inf by the same call and then, for every view and every valid
+ *   face whose three corners a, b, c are projectable and whose area2 is < 0 or > 0 (both orientations: back faces occlude too):
+ *     x runs over max(0, ceilf(min(ax, bx, cx))) .. min(w - 1, floorf(max(ax, bx, cx))), y likewise, the bounds compared as floats
+ *     before any conversion to an integer;
+ *     wa = E_bc(x, y), wb = E_ca(x, y), wc = E_ab(x, y) with (float) x, (float) y;  the pixel is COVERED iff all three are >= 0
+ *     (area2 > 0) or all three are <= 0 (area2 < 0): a pixel centre on an edge belongs to both faces of the edge;
+ *     iz = ((wa*(1/depth_a) + wb*(1/depth_b)) + wc*(1/depth_c)) / area2,  d = 1/iz;
+ *     if d is finite and > 0:  zbuf[v][y][x] = min(zbuf[v][y][x], d), an unsigned 32-bit atomic minimum on the bits (positive floats
+ *     order as their bits).
+ *   A face with a corner that is not projectable is skipped in that view.  THERE IS NO NEAR-PLANE CLIPPING: the cameras stand
+ *   outside the surface, and a face that crosses a camera's plane z = 0 does not occlude in that camera.  Any triangle is handled,
+ *   one that covers the whole frame included; no loop exceeds w * h steps.  No workspace: the corners are projected per face.
+ *
+ * sfm_mesh_face_views — face_view_dev int32 [nf_cap], face_score_dev float32 [nf_cap]; zbuf_dev as sfm_mesh_render_depth left it;
+ *   vis_tol >= 0 (finite).  A valid face is a CANDIDATE of view v iff
+ *     its three corners are projectable and lie in 0 <= sx <= w - 1, 0 <= sy <= h - 1;
+ *     area2 < 0 (sfm_mesh_extract winds faces with the normal toward the cameras; with x right, y down, z forward that is a
+ *     negative screen area);
+ *     it is VISIBLE: each of four samples, the three corners and the centroid g_c = ((a_c + b_c) + c_c) / 3.0f of the positions
+ *     (projected like a vertex), is projectable, its nearest pixel (rintf(sx), rintf(sy)) lies in the frame (compared as floats)
+ *     and depth <= zbuf[v][py][px] * (1.0f + vis_tol).  An empty pixel holds +inf and passes.
+ *   score = -area2.  face_view = the candidate view of the largest score, the lowest index among equal scores; -1 and score 0 when
+ *   there is none or the face is not valid.  Rows at or past nf are never written.  No atomics.
+ *
+ * sfm_mesh_texture_fill — atlas_dev [side][side][3] uint8 B G R.  The layout is a function of (nf_cap, texels) alone, texels = L the
+ *   texels per triangle leg, 1 <= L <= 64:  cell side c = L + 5;  cols = the smallest integer >= 1 with cols^2 >= ceil(nf_cap / 2);
+ *   side = cols * c <= 16384.  Face f owns half `f & 1` of cell q = f >> 1 whose origin is ((q % cols)*c, (q / cols)*c); in the
+ *   cell's texel coordinates (i, j), half 0 owns i + j <= c - 1 and half 1 the rest.  Corners a, b, c of the face sit at
+ *     half 0:  (1, 1), (1 + L, 1), (1, 1 + L)        half 1:  (c - 2, c - 2), (c - 2 - L, c - 2), (c - 2, c - 2 - L)
+ *   so that a chart keeps at least one texel to the diagonal and to the cell's border; those texels are filled by the same
+ *   formula, extrapolated, which dilates the chart against bleeding under bilinear lookups.  Per texel, row-major:
+ *     half 0:  u = (float)(i - 1) / (float)L,  v = (float)(j - 1) / (float)L;   half 1:  u = (float)(c - 2 - i) / (float)L,
+ *     v = (float)(c - 2 - j) / (float)L;   w0 = (1.0f - u) - v;   X_c = (w0*A_c + u*B_c) + v*C_c per coordinate;
+ *     if k = face_view_dev[f] lies in 0..n-1: X is projected by P_k (projectable or not) and frame k, frames_dev [n][h][w][3] uint8,
+ *     is sampled:  sx clamped to [0, w - 1] and sy to [0, h - 1] (NaN -> 0);  x0 = min((int)floorf(sx), w - 2),  fx = sx - (float)x0,
+ *     y0, fy likewise;  value = ((p00*(1 - fx) + p10*fx)*(1 - fy)) + ((p01*(1 - fx) + p11*fx)*fy) per channel, p10 = pixel (x0 + 1, y0);
+ *     otherwise, with colors_dev [nv_cap][3] float32 given, value = (w0*Ca + u*Cb) + v*Cc per channel, and without it 0;
+ *     texel = (uint8) min(max(rintf(value), 0), 255)  (NaN -> 0).
+ *   Texels of faces at or past nf, of cells past the last face and of faces that are not valid are 0.
+ * Errors (SFM_ERR_ARG, before any device call): a capacity negative or above 2^31 - 1; n outside 1..65536; w or h < 2 or
+ *   w * h > 2^26; vis_tol negative or not finite; texels outside 1..64, a layout whose side exceeds 16384, cols or side that
+ *   disagree with the layout; NULL where required (vertices with nv_cap, faces, face_view_dev and face_score_dev with nf_cap; P_dev,
+ *   zbuf_dev, frames_dev and atlas_dev always).  None of the three takes a workspace.
+ * ---------------------------------------------------------------------- */
+int sfm_mesh_render_depth(const float* vertices_dev, const int32_t* faces_dev, int64_t nv_cap, int64_t nf_cap, const int32_t* counts_dev,
+                          const float* P_dev, int n, int64_t w, int64_t h, float* zbuf_dev, void* stream);
+int sfm_mesh_face_views(const float* vertices_dev, const int32_t* faces_dev, int64_t nv_cap, int64_t nf_cap, const int32_t* counts_dev,
+                        const float* P_dev, int n, int64_t w, int64_t h, const float* zbuf_dev, float vis_tol, int32_t* face_view_dev,
+                        float* face_score_dev, void* stream);
+int sfm_mesh_texture_fill(const float* vertices_dev, const float* colors_dev, const int32_t* faces_dev, int64_t nv_cap, int64_t nf_cap,
+                          const int32_t* counts_dev, const float* P_dev, const uint8_t* frames_dev, int n, int64_t w, int64_t h,
+                          const int32_t* face_view_dev, int texels, int cols, int side, uint8_t* atlas_dev, void* stream);
+
+/* ------------------------------------------------------------------------
  * Measurement hook (no reference counterpart): when enabled, the library brackets
  * its dominant kernels with hipEvents recorded on the launch stream.
  * sfm_profile_read synchronises those events, returns the summed device time

@@ -109,6 +109,9 @@ SIGNATURES = {
     "sfm_mesh_smooth": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
     "sfm_mesh_decimate_ws_bytes": (_sz, [_i64, _i64, _vp]),
     "sfm_mesh_decimate": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _vp, _f32, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_mesh_render_depth": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
+    "sfm_mesh_face_views": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _i64, _i64, _vp, _f32, _vp, _vp, _vp]),
+    "sfm_mesh_texture_fill": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _vp, _int, _int, _int, _vp, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

@@ -7,7 +7,9 @@ tensors in, device tensors out, stream ordered, no CPU path.  The host part is t
 Opt-in after the extraction: `mesh_components` / `clean_mesh` (sfm_mesh_components, sfm_mesh_clean; "MESH-CLEAN") drop the small
 connected components, `run_mesh(clean=True)` (docs/mesh.md §7); `smooth_mesh` / `mesh_normals` (sfm_mesh_smooth, sfm_mesh_normals;
 "MESH-FINISH") smooth the surface and give it vertex normals, `run_mesh(smooth=..., normals=True)` (docs/mesh.md §8);
-`decimate_mesh` (sfm_mesh_decimate; "MESH-DECIMATE") simplifies it by vertex clustering, `run_mesh(decimate=...)` (docs/mesh.md §9).
+`decimate_mesh` (sfm_mesh_decimate; "MESH-DECIMATE") simplifies it by vertex clustering, `run_mesh(decimate=...)` (docs/mesh.md §9);
+`render_depth`, `face_views`, `texture_fill` / `texture_mesh` (sfm_mesh_render_depth, sfm_mesh_face_views, sfm_mesh_texture_fill;
+"MESH-TEXTURE") give it a texture atlas from the photographs, `run_mesh(texture=True)` (docs/mesh.md §10).
 """
 import numpy as np
 import torch
@@ -35,6 +37,12 @@ SMOOTH_PAIRS = 10               # the pair count the calibration recommends (doc
 # Decimation (include/sfm_hip.h, "MESH-DECIMATE"; docs/mesh.md §9).
 MAX_CELLS = 1 << 27             # cells per clustering grid
 DECIMATE_CELLS = 2.0            # the cell size in voxels the calibration recommends (docs/mesh.md §9); run_mesh's own default stays 0
+
+# Texturing (include/sfm_hip.h, "MESH-TEXTURE"; docs/mesh.md §10).
+ATLAS_TEXELS = 8                # texels per triangle leg: the atlas of k faces has a side of about sqrt(k / 2) * 13
+MAX_ATLAS_TEXELS = 64
+MAX_ATLAS_SIDE = 16384
+VIS_TOL = 0.02                  # relative depth tolerance of the visibility test, calibrated (scripts/calibrate_mesh_texture.py)
 
 
 def volume_bounds(points, resolution=256, pad=0.05):
@@ -348,6 +356,194 @@ def decimate_mesh(vertices, colors, faces, origin, cell, dims, extent, dedupe=Tr
     return (out_v, out_c, out_f, out_n, buf) if packed else (out_v, out_c, out_f, out_n)
 
 
+def _layout(nf, texels):
+    nf, L = int(nf), int(texels)
+    if not 1 <= L <= MAX_ATLAS_TEXELS:
+        raise SfmHipError(f"atlas_layout: texels {texels} must be in 1..{MAX_ATLAS_TEXELS}")
+    if nf < 0:
+        raise SfmHipError(f"atlas_layout: {nf} faces")
+    slots = (nf + 1) // 2
+    cols = int(np.sqrt(float(slots)))
+    while cols * cols < slots:
+        cols += 1
+    while cols > 1 and (cols - 1) * (cols - 1) >= slots:
+        cols -= 1
+    cols, cell = max(cols, 1), L + 5
+    if cols * cell > MAX_ATLAS_SIDE:
+        raise SfmHipError(f"atlas_layout: {nf} faces at {L} texels need a side of {cols * cell} > {MAX_ATLAS_SIDE}; lower texels or decimate")
+    return cols * cell, cols, cell
+
+
+def atlas_layout(nf, texels=ATLAS_TEXELS):
+    """The atlas of `nf` faces at `texels` (1..64) texels per triangle leg (include/sfm_hip.h, "MESH-TEXTURE"): every face owns half
+    of a square cell of texels + 5 texels a side, the cells fill a square of cols x cols row by row.
+    Returns (side, cols, cell, uv): uv (nf, 3, 2) float64, the texture coordinates ((ox + i + 0.5) / side, 1 - (oy + j + 0.5) / side)
+    of the three corners of every face (v up, as OBJ has it).  Host only.  Raises SfmHipError when texels is out of range or the
+    side would exceed 16384."""
+    side, cols, cell = _layout(nf, texels)
+    nf, L = int(nf), int(texels)
+    f = np.arange(nf)
+    q, half = f >> 1, (f & 1)[:, None]
+    ox, oy = ((q % cols) * cell)[:, None], ((q // cols) * cell)[:, None]
+    ci = np.where(half == 0, np.array([1, 1 + L, 1]), np.array([cell - 2, cell - 2 - L, cell - 2]))
+    cj = np.where(half == 0, np.array([1, 1, 1 + L]), np.array([cell - 2, cell - 2, cell - 2 - L]))
+    uv = np.stack([(ox + ci + 0.5) / side, 1.0 - (oy + cj + 0.5) / side], -1).reshape(nf, 3, 2)
+    return side, cols, cell, uv
+
+
+def _view_rows(P, dev, what):
+    if torch.is_tensor(P):
+        require_cuda(P)
+        Pd = P.to(dev, torch.float32).contiguous().reshape(-1, 12)
+    else:
+        Pd = _upload(np.ascontiguousarray(np.asarray(P, np.float32).reshape(-1, 12)), dev)
+    if Pd.shape[0] < 1:
+        raise SfmHipError(f"{what}: needs at least one view")
+    return Pd
+
+
+def render_depth(vertices, faces, P, w, h, counts=None, out=None):
+    """A depth map of the mesh in every view (sfm_mesh_render_depth): per pixel the smallest camera depth of the faces that cover
+    its centre, +inf where none does; both orientations are drawn and nothing is clipped at the near plane.  vertices [m, 3]
+    float32, faces [k, 3] int32 device tensors; P float32 [n, 12] (projection_rows: a host array, uploaded through pinned memory, or
+    a device tensor); counts as in mesh_normals.  Returns an [n, h, w] float32 device tensor (`out` when given).  No host wait; the
+    words do not depend on the order in which anything lands."""
+    vertices, faces = _finish_args(vertices, faces, counts, "render_depth")
+    dev = vertices.device
+    Pd = _view_rows(P, dev, "render_depth")
+    n, w, h = int(Pd.shape[0]), int(w), int(h)
+    if w < 2 or h < 2 or w * h > (1 << 26):
+        raise SfmHipError(f"render_depth: frame {w} x {h}: w and h must be >= 2 and w * h <= 2^26")
+    if out is None:
+        out = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, h, w) or not out.is_contiguous() or out.device != dev:
+        raise SfmHipError("render_depth: out must be a contiguous [n, h, w] float32 tensor on the vertices' device")
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    with on_device(dev):
+        check(_lib.lib().sfm_mesh_render_depth(ptr(vertices) if nv else None, ptr(faces) if nf else None, nv, nf, ptr(counts), ptr(Pd), n, w, h,
+                                               ptr(out), stream_ptr()), "sfm_mesh_render_depth")
+    return out
+
+
+def face_views(vertices, faces, P, zbuf, vis_tol=VIS_TOL, counts=None):
+    """The view every face is textured from (sfm_mesh_face_views): among the views in which the face lies in the frame, faces the
+    camera (negative screen area) and is visible in render_depth's `zbuf` [n, h, w] at its corners and its centroid within the
+    relative tolerance `vis_tol`, the one in which it is largest (the lowest index on ties).  Returns (face_view int32 [k], -1
+    where there is none; face_score float32 [k], the screen area doubled) device tensors of which the counted rows are written.
+    No host wait."""
+    vertices, faces = _finish_args(vertices, faces, counts, "face_views")
+    dev = vertices.device
+    Pd = _view_rows(P, dev, "face_views")
+    require_cuda(zbuf)
+    if zbuf.dtype != torch.float32 or zbuf.dim() != 3 or zbuf.shape[0] != Pd.shape[0] or not zbuf.is_contiguous() or zbuf.device != dev:
+        raise SfmHipError("face_views: zbuf must be render_depth's contiguous [n, h, w] float32 tensor for the same views")
+    vis_tol = float(vis_tol)
+    if not (np.isfinite(vis_tol) and vis_tol >= 0.0):
+        raise SfmHipError(f"face_views: vis_tol {vis_tol} must be finite and >= 0")
+    n, h, w = (int(d) for d in zbuf.shape)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    view = torch.empty(nf, dtype=torch.int32, device=dev)
+    score = torch.empty(nf, dtype=torch.float32, device=dev)
+    with on_device(dev):
+        check(_lib.lib().sfm_mesh_face_views(ptr(vertices) if nv else None, ptr(faces) if nf else None, nv, nf, ptr(counts), ptr(Pd), n, w, h,
+                                             ptr(zbuf), vis_tol, ptr(view) if nf else None, ptr(score) if nf else None, stream_ptr()),
+              "sfm_mesh_face_views")
+    return view, score
+
+
+def texture_fill(vertices, colors, faces, P, frames, face_view, texels=ATLAS_TEXELS, counts=None, out=None):
+    """The atlas (sfm_mesh_texture_fill): every texel of atlas_layout(k, texels) is the bilinear sample of frame face_view[f] at the
+    projection of the texel's point on its face f; faces without a view interpolate the vertex `colors` ([m, 3] float32 B G R, or
+    None: 0).  frames [n, h, w, 3] uint8 B G R, face_view int32 [k]: device tensors.  Returns a [side, side, 3] uint8 device
+    tensor (`out` when given, every texel written).  No host wait."""
+    vertices, faces = _finish_args(vertices, faces, counts, "texture_fill")
+    dev = vertices.device
+    require_cuda(colors, frames, face_view)
+    if colors is not None and (colors.dtype != torch.float32 or colors.shape != vertices.shape or colors.device != dev):
+        raise SfmHipError("texture_fill: colors must be [m, 3] float32 like the vertices")
+    colors = None if colors is None else colors.contiguous()
+    Pd = _view_rows(P, dev, "texture_fill")
+    n = int(Pd.shape[0])
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[0] != n or frames.shape[3] != 3 or frames.device != dev:
+        raise SfmHipError("texture_fill: frames must be an [n, h, w, 3] uint8 device tensor, one frame per view")
+    frames = frames.contiguous()
+    h, w = int(frames.shape[1]), int(frames.shape[2])
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    if face_view.dtype != torch.int32 or tuple(face_view.shape) != (nf,) or not face_view.is_contiguous() or face_view.device != dev:
+        raise SfmHipError("texture_fill: face_view must be a contiguous int32 [k] tensor on the vertices' device")
+    side, cols, _ = _layout(nf, texels)
+    if out is None:
+        out = torch.empty((side, side, 3), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (side, side, 3) or not out.is_contiguous() or out.device != dev:
+        raise SfmHipError(f"texture_fill: out must be a contiguous [{side}, {side}, 3] uint8 tensor on the vertices' device")
+    with on_device(dev):
+        check(_lib.lib().sfm_mesh_texture_fill(ptr(vertices) if nv else None, ptr(colors), ptr(faces) if nf else None, nv, nf, ptr(counts),
+                                               ptr(Pd), ptr(frames), n, w, h, ptr(face_view) if nf else None, int(texels), cols, side, ptr(out),
+                                               stream_ptr()), "sfm_mesh_texture_fill")
+    return out
+
+
+def _frames_tensor(images, dev, what):
+    if torch.is_tensor(images):
+        frames = images.to(dev)
+    elif all(torch.is_tensor(im) and im.is_cuda for im in images):
+        frames = torch.stack([im.to(dev) for im in images])
+    else:
+        host = [im.cpu().numpy() if torch.is_tensor(im) else np.asarray(im) for im in images]
+        if any(im.shape != host[0].shape or im.dtype != np.uint8 for im in host):
+            raise SfmHipError(f"{what}: frames must be (H, W, 3) uint8 BGR of one size")
+        frames = _upload(np.stack(host), dev)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+        raise SfmHipError(f"{what}: frames must be (H, W, 3) uint8 BGR of one size")
+    return frames.contiguous()
+
+
+def _device_rows(a, integer, dev):
+    """[m, 3] float32 (int32 when `integer`) on the device: a device tensor as it is, a host array through pinned memory."""
+    if torch.is_tensor(a):
+        require_cuda(a)
+        return a.to(dev, torch.int32 if integer else torch.float32).contiguous()
+    return _upload(np.ascontiguousarray(np.asarray(a).reshape(-1, 3).astype(np.int32 if integer else np.float32)), dev)
+
+
+def texture_mesh(vertices, colors, faces, images, K, Ps, texels=ATLAS_TEXELS, vis_tol=VIS_TOL):
+    """A texture atlas for a mesh from its photographs: render_depth, face_views and texture_fill enqueued one after another, then
+    ONE download (the atlas and the faces' views in one buffer): the only host wait.
+    vertices (m, 3), colors (m, 3) B G R or None, faces (k, 3): host arrays (uploaded through pinned memory on the stream) or
+    device tensors; images: n BGR uint8 frames of one size (host arrays, device tensors, or one [n, h, w, 3] device tensor);
+    K (3, 3), Ps (n, 3, 4) = K [R|t] per camera in the images' order (what posearr stores: projection_rows).
+    Returns dict(atlas (side, side, 3) uint8 B G R, uv (k, 3, 2) float64 (atlas_layout), face_view int32 (k,), -1 where no view
+    shows the face (its chart interpolates the vertex colours), textured: the faces with a view)."""
+    dev = next((t.device for t in (vertices, faces) if torch.is_tensor(t) and t.is_cuda), None)
+    if dev is None:
+        dev = next((im.device for im in ([images] if torch.is_tensor(images) else images) if torch.is_tensor(im) and im.is_cuda),
+                   torch.device("cuda", torch.cuda.current_device()))
+    rows = projection_rows(K, Ps)
+    with torch.cuda.device(dev):
+        v, f = _device_rows(vertices, False, dev), _device_rows(faces, True, dev)
+        c = None if colors is None else _device_rows(colors, False, dev)
+        frames = _frames_tensor(images, dev, "texture_mesh")
+        return _texture(v, c, f, frames, _upload(rows, dev), texels, vis_tol)
+
+
+def _texture(v, c, f, frames, Pd, texels, vis_tol):
+    """texture_mesh on device tensors."""
+    if Pd.shape[0] != frames.shape[0]:
+        raise SfmHipError(f"texture_mesh: {frames.shape[0]} frames for {Pd.shape[0]} cameras")
+    nf, dev = int(f.shape[0]), v.device
+    side, cols, cell, uv = atlas_layout(nf, texels)
+    head = (4 * nf + 255) // 256 * 256
+    buf = torch.empty(head + 3 * side * side, dtype=torch.uint8, device=dev)
+    view = buf[:4 * nf].view(torch.int32)
+    zbuf = render_depth(v, f, Pd, int(frames.shape[2]), int(frames.shape[1]))
+    got, _ = face_views(v, f, Pd, zbuf, vis_tol)
+    view.copy_(got)
+    texture_fill(v, c, f, Pd, frames, view, texels, out=buf[head:].view(side, side, 3))
+    host = buf.cpu().numpy()                                        # the one download
+    fv = np.ascontiguousarray(host[:4 * nf]).view(np.int32)
+    return dict(atlas=np.ascontiguousarray(host[head:].reshape(side, side, 3)), uv=uv, face_view=fv, textured=int((fv >= 0).sum()))
+
+
 def decimate_frame(origin, voxel, dims, decimate):
     """run_mesh's clustering grid for a volume (origin (3,) float64, voxel, dims) and a cell of `decimate` voxels: (origin float64
     (3,), cell, dims, extent).  The grid starts one cell below the volume's origin and has floor((dims_c - 1) * voxel / cell) + 3
@@ -366,7 +562,8 @@ def decimate_frame(origin, voxel, dims, decimate):
 
 def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOXELS, w_min=W_MIN, tau=0.01, min_consistent=2, nsrc=4,
              pad=0.05, clean=False, min_component_share=MIN_COMPONENT_SHARE, min_component_faces=None, largest_only=False, normals=False,
-             smooth=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, decimate=0, decimate_dedupe=True):
+             smooth=0, smooth_lambda=SMOOTH_LAMBDA, smooth_mu=SMOOTH_MU, decimate=0, decimate_dedupe=True, texture=False,
+             texture_texels=ATLAS_TEXELS, texture_vis_tol=VIS_TOL):
     """A coloured triangle mesh of a registered sequence from run_mvs's depth maps.
 
     images:  the BGR uint8 frames run_mvs got (device tensors or host arrays, K's resolution, posearr's camera order)
@@ -385,6 +582,11 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     output once); vertices, colors, faces and normals then describe the decimated mesh, and the dict gains `decimated_from`
     (vertices, faces) before the step and `decimate_unusable`, the vertices that fell outside the grid.  Off by default
     (DECIMATE_CELLS is the recommended cell, docs/mesh.md §9); no host wait is added and the rows before the step are not downloaded.
+    texture=True: then, after the download, the final surface (after the clean-up, the smoothing and the decimation) gets a texture
+    atlas from the frames, which are already on the device (texture_mesh's three steps at `texture_texels` texels per triangle
+    leg and the visibility tolerance `texture_vis_tol`; the final rows go back up through pinned memory on the stream), and the
+    dict gains `atlas` (side, side, 3) uint8 B G R, `uv` (k, 3, 2) float64 and `face_view` int32 (k,) for pipeline.to_obj_mesh.
+    Off by default (docs/mesh.md §10); on, it adds exactly one host wait: the download of the atlas.
     Returns dict(vertices (m, 3) float64, colors (m, 3) float64 B G R, faces (k, 3) int32) for pipeline.to_ply_mesh.
     Two host waits per call: the mesh totals and the one download; every upload is stream-ordered (pinned memory).  (Should the
     downloaded labelling status say "not converged" the labelling is continued, and cleaned and downloaded again, until it has.)"""
@@ -407,6 +609,10 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     dec = None
     if decimate != 0:
         dec = dict(frame=decimate_frame(origin, voxel, dims, decimate), dedupe=bool(decimate_dedupe))
+    if texture:
+        _layout(0, texture_texels)                                  # the range of texels, before any work
+        if not (np.isfinite(float(texture_vis_tol)) and float(texture_vis_tol) >= 0.0):
+            raise SfmHipError(f"run_mesh: texture_vis_tol {texture_vis_tol} must be finite and >= 0")
     dev = depths[0].device
     require_cuda(*depths)
     if all(torch.is_tensor(im) and im.is_cuda for im in images):
@@ -422,21 +628,33 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
     nsrc = min(int(nsrc), n - 1, mvs.MAX_VIEWS)
     masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    rows = projection_rows(K, Ps)
+
+    def textured(out):
+        """run_mesh's dict, with the atlas of its surface when texture is on (enqueued after the download, one more download)."""
+        if not texture:
+            return out
+        with torch.cuda.device(dev):
+            v, c, f = _device_rows(out["vertices"], False, dev), _device_rows(out["colors"], False, dev), _device_rows(out["faces"], True, dev)
+            tex = _texture(v, c, f, frames, _upload(rows, dev), texture_texels, texture_vis_tol)
+        out.update(atlas=tex["atlas"], uv=tex["uv"], face_view=tex["face_view"])
+        return out
+
     with torch.cuda.device(dev):
         for i in range(n):
             nb = mvs.neighbours(i, n, nsrc)
             ab, bc = mvs.consistency_matrices(K, Ps[i], Ps[nb])
             mvs.consistency(depths[i], [depths[v] for v in nb], nb, ab, i, bc, tau, min(int(min_consistent), len(nb)), False,
                             mask_out=masks[i], xyz_out=xyz[i])
-        S, W, C = tsdf_integrate(torch.stack(depths), projection_rows(K, Ps), origin, voxel, dims, float(trunc_voxels) * voxel,
+        S, W, C = tsdf_integrate(torch.stack(depths), rows, origin, voxel, dims, float(trunc_voxels) * voxel,
                                  masks=masks, bgr=frames)
         verts, cols, faces, buf = extract_mesh(S, W, C, origin, voxel, w_min, packed=True)
         if clean:
-            return _clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish, dec)
+            return textured(_clean_and_download(verts, cols, faces, min_component_share, min_component_faces, largest_only, finish, dec))
         if dec is not None:
             parts = _decimate(verts, cols, faces, None, finish, dec)
             host = (torch.cat(parts) if len(parts) > 1 else parts[0]).cpu().numpy()     # the one download
-            return _decimated_rows(host, len(verts), len(faces), (len(verts), len(faces)), finish)
+            return textured(_decimated_rows(host, len(verts), len(faces), (len(verts), len(faces)), finish))
         if finish is not None:
             buf = torch.cat([buf] + _finish(verts, faces, None, finish))
         host = buf.cpu().numpy()                                    # the one download
@@ -446,7 +664,7 @@ def run_mesh(images, K, posearr, mvs_out, resolution=256, trunc_voxels=TRUNC_VOX
                faces=np.ascontiguousarray(host[6 * nv:6 * nv + 3 * nt].reshape(nt, 3)))
     if finish is not None:
         out.update(_finished_rows(host[6 * nv + 3 * nt:], nv, nv, finish))
-    return out
+    return textured(out)
 
 
 def _finish(verts, faces, counts, finish):

@@ -672,6 +672,63 @@ def to_ply_mesh(path, vertices, colors, faces, normals=None):
     return len(verts), len(tris)
 
 
+def png_bytes(rgb):
+    """An (h, w, 3) uint8 R G B array as an 8-bit truecolour PNG, rows top to bottom, filter 0: the standard library only."""
+    import struct
+    import zlib
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    h, w = rgb.shape[:2]
+    raw = np.concatenate([np.zeros((h, 1), np.uint8), rgb.reshape(h, 3 * w)], axis=1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6))
+            + chunk(b"IEND", b""))
+
+
+def to_obj_mesh(path, vertices, faces, uv, atlas, normals=None):
+    """The textured surface of mesh.run_mesh(texture=True) as three files under Point_Cloud/: dense_mesh.obj (`v` x200 as
+    to_ply_mesh, one `vt` per face corner from `uv` (k, 3, 2), `vn` per vertex when `normals` is given, `f a/ta b/tb c/tc` or
+    `f a/ta/a ...`, 1-based), dense_mesh.mtl (`map_Kd dense_mesh.png`) and dense_mesh.png (the (side, side, 3) B G R `atlas` as
+    R G B, rows top to bottom, written with zlib and struct alone).  Returns (vertices, faces) written."""
+    verts = np.asarray(vertices, np.float64).reshape(-1, 3) * 200
+    tris = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    uv = np.asarray(uv, np.float64).reshape(-1, 3, 2)
+    atlas = np.asarray(atlas)
+    if len(uv) != len(tris):
+        raise ValueError(f"to_obj_mesh: {len(tris)} faces but texture coordinates of {len(uv)}")
+    if len(tris) and (tris.min() < 0 or tris.max() >= len(verts)):
+        raise ValueError("to_obj_mesh: a face names a vertex that does not exist")
+    if atlas.dtype != np.uint8 or atlas.ndim != 3 or atlas.shape[2] != 3:
+        raise ValueError("to_obj_mesh: the atlas must be (side, side, 3) uint8")
+    if normals is not None:
+        nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+        if len(nrm) != len(verts):
+            raise ValueError(f"to_obj_mesh: {len(verts)} vertices but {len(nrm)} normals")
+    base = path + "/Point_Cloud/dense_mesh"
+    with open(base + ".png", "wb") as f:
+        f.write(png_bytes(atlas[..., ::-1]))
+    with open(base + ".mtl", "w") as f:
+        f.write("newmtl dense_mesh\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd dense_mesh.png\n")
+    with open(base + ".obj", "w") as f:
+        f.write("mtllib dense_mesh.mtl\nusemtl dense_mesh\n")
+        if len(verts):
+            np.savetxt(f, verts, "v %f %f %f")
+        if len(tris):
+            np.savetxt(f, uv.reshape(-1, 2), "vt %.9f %.9f")
+        if normals is not None and len(verts):
+            np.savetxt(f, nrm, "vn %f %f %f")
+        if len(tris):
+            t = 3 * np.arange(len(tris))[:, None] + np.array([1, 2, 3])
+            a = tris + 1
+            if normals is not None:
+                np.savetxt(f, np.stack([a, t, a], -1).reshape(-1, 9), "f %d/%d/%d %d/%d/%d %d/%d/%d")
+            else:
+                np.savetxt(f, np.stack([a, t], -1).reshape(-1, 6), "f %d/%d %d/%d %d/%d")
+    return len(verts), len(tris)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The incremental driver (sfm.py:274-423, bundle_adjustment=False: the reference's default), written ONCE over a small
 # engine interface.  An engine owns the array type the per-frame state lives in and supplies the operators:
