@@ -919,6 +919,91 @@ int sfm_mesh_texture_fill(const float* vertices_dev, const float* colors_dev, co
  * launch are amortised; sfm_profile_read then reports n launches per bracket.
  * ---------------------------------------------------------------------- */
 int sfm_profile_enable(int on);
+
+/* ------------------------------------------------------------------------
+ * TRACKS (no reference counterpart: isfm.py:56-94 matches and verifies every pair and ends there; csrc/tracks.hip, docs/tracks.md):
+ * feature tracks, scene points followed through all the images that see them, from the match store of all pairs, and their
+ * N-view triangulation.  Every integer output below is a minimum, a count, a rank or a copy of its inputs: no word depends on
+ * the order in which atomics land.  Every float64 operation of the triangulation is correctly rounded in the order written here
+ * (no FMA, no reassociation, IEEE / and sqrt).  tests/np_tracks.py restates every output exactly.
+ *
+ *   node        img_off[image] + keypoint.  img_off_dev int32 [n_img + 1], img_off[0] = 0, non-decreasing (an image may be empty),
+ *               N = img_off[n_img] = n_nodes <= 2^31 - 1;  1 <= n_img <= 65 536.  The image of node u is the largest i < n_img with
+ *               img_off[i] <= u, found by binary search (at most 17 steps).
+ *
+ * sfm_match_edges — the match store as edges, with no compaction and no host wait: one item per (pair p, slot q < cap).
+ *   store_dev   int32 [n_pairs][2][cap][2] as sharded.match_pairs_sharded leaves it: [p][0][q] = the two trainIdx, [p][1][q] = the
+ *               bits of the two float32 distances (d0, d1).  pair_img_dev int32 [n_pairs][2], nq_dev int32 [n_pairs]: on the device.
+ *   survivor    q < nq[p], both images of the pair in 0..n_img-1, q below the size of the first and trainIdx0 in 0..size-1 of the
+ *               second, a second neighbour (trainIdx1 >= 0), (double)d0 < ratio * (double)d1 (the rule of sfm_ratio_compact), and,
+ *               when keep_dev (uint8 [n_pairs][cap], optional) is given, keep[p][q] != 0.
+ *   edges_dev   int32 [n_pairs * cap][2]: a survivor writes (img_off[pair[p][0]] + q, img_off[pair[p][1]] + trainIdx0) at p * cap + q,
+ *               every other slot (-1, -1).  n_pairs * cap <= 2^31 - 1.
+ *
+ * sfm_track_components — label[u] = the smallest node id of u's component over the VALID edges; the contract of sfm_mesh_components.
+ *   valid edge  both ends lie in 0..N-1 and differ.  An invalid edge joins nothing and is never dereferenced; duplicates are harmless.
+ *   a round     per valid edge m = min(label[a], label[b]): the end with the larger label and that label's own entry are lowered
+ *               to m (a read first, an atomic min only when it can lower); per node label[u] is lowered to where
+ *               label[label[..]] leads within 4 hops.  `rounds` (1..1024) launches are enqueued with no host wait; a round that
+ *               lowers nothing ends the work: the later launches return at once.
+ *   labels_dev  [N] int32.  resume == 0: started from label[u] = u; otherwise continued from a state an earlier call left.
+ *   status_dev  int32[2] = (converged 0/1, rounds that lowered a label).  Unconverged labels are a valid state to resume from:
+ *               every label is a node of the node's own component, >= its minimum and <= the node.
+ *
+ * sfm_track_build — labels_dev must be converged (otherwise the outputs are unspecified, though every write stays in bounds).
+ *   candidate   a component with >= 2 nodes.  conflicting: two of its nodes lie in one image (decided per (label, image) by an
+ *               open-addressing set that holds the smallest node of each pair).  kept: a candidate that is not conflicting with
+ *               min_len <= size <= max_len (2 <= min_len <= max_len <= 2^31 - 1).
+ *   tracks      the kept components in ascending label order are tracks 0..T-1.
+ *   node_track_dev int32 [N]: the node's track or -1.   track_off_dev int32 [N / 2 + 2], of which T + 1 words are written.
+ *   obs_node_dev   int32 [N], of which nobs = track_off[T] are written: a track's nodes in ascending id, hence ascending image.
+ *   counts_dev  int32[6] = (T, nobs, candidates, conflicting, longest kept, nodes in components of one node).  The first two
+ *               words are what sfm_track_triangulate reads on the device.  Nothing at or past the counted rows is written.
+ *
+ * sfm_track_triangulate — one lane per track t < counts[0] (a count outside 0..N/2+1, or nobs outside 0..N, is taken as that
+ *   capacity; offsets are clamped to 0 <= lo <= hi <= nobs).  kp_dev float32 [N][2], all images concatenated; P_dev float64
+ *   [n_img][12], row-major 3 x 4.  In observation order, with (x, y) = the keypoint promoted to float64 and P the image's matrix:
+ *     r0[k] = x * P[8 + k] - P[k],  r1[k] = y * P[8 + k] - P[4 + k]   (k = 0..3: the rows of the rows = 4 DLT, not normalised)
+ *     M[a][b] = (M[a][b] + r0[a] * r0[b]) + r1[a] * r1[b]             for a <= b, from M = 0; then M[b][a] = M[a][b]
+ *   (an observation whose node lies outside 0..N-1 adds nothing).  Eigenvectors by cyclic Jacobi on the 4 x 4, V = I:
+ *     sweeps      at most 30; a sweep visits the pivots (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); the sweep in which no pivot rotates
+ *                 is the last.
+ *     a pivot     (p, q), apq = M[p][q], app = M[p][p], aqq = M[q][q], is SKIPPED when apq == 0 or
+ *                 |apq| <= 2^-52 * sqrt(|app| * |aqq|).  Otherwise
+ *                   theta = (aqq - app) / (2 * apq);  root = sqrt(theta * theta + 1)
+ *                   t = theta >= 0 ? 1 / (theta + root) : -1 / (root - theta);  c = 1 / sqrt(t * t + 1);  s = t * c
+ *                   for k not in {p, q}:  M[k][p] = M[p][k] = c * akp - s * akq;  M[k][q] = M[q][k] = s * akp + c * akq
+ *                                         (akp, akq = the old M[k][p], M[k][q])
+ *                   M[p][p] = app - t * apq;  M[q][q] = aqq + t * apq;  M[p][q] = M[q][p] = 0
+ *                   for k = 0..3:         V[k][p] = c * vkp - s * vkq;  V[k][q] = s * vkp + c * vkq
+ *     the vector  v = column j of V, j = the index of the smallest M[j][j] (ties: the lowest j).
+ *   X_dev       float32 [N / 2 + 1][3]: X[c] = (float)(v[c] / v[3]).
+ *   err_dev, depth_dev  float32 [N] per observation, with (Xd, Yd, Zd) = X promoted to float64 and P its image's matrix:
+ *                 h_r = ((P[4r] * Xd + P[4r + 1] * Yd) + P[4r + 2] * Zd) + P[4r + 3];   depth = (float)h_2
+ *                 du = h_0 / h_2 - x;  dv = h_1 / h_2 - y;  err = (float)sqrt(du * du + dv * dv)
+ *               (both NaN for a node outside 0..N-1).
+ *   flags_dev   int32 [N / 2 + 1]: bit 0 = every depth of the track is finite and > 0; bit 1 = v[3] != 0 and X is finite.
+ *   max_err_dev float32 [N / 2 + 1]: from m = 0, in observation order, m = err when err > m or err is NaN (a NaN stays).
+ *   Every float32 NaN that is written is the quiet NaN 0x7FC00000.
+ *
+ * Errors (SFM_ERR_ARG, before any device call): negative counts or counts above 2^31 - 1, n_pairs * cap above 2^31 - 1, n_img
+ *   outside 1..65 536, a NaN ratio, rounds outside 1..1024, min_len / max_len outside 2 <= min_len <= max_len <= 2^31 - 1, NULL where
+ *   the count is non-zero (img_off_dev, status_dev, counts_dev, track_off_dev, P_dev, X_dev, flags_dev, max_err_dev and the
+ *   workspaces always), a workspace smaller than the _ws_bytes twin says.  The _ws_bytes twins return 0 for invalid sizes.
+ * ---------------------------------------------------------------------- */
+int sfm_match_edges(const int32_t* store_dev, int64_t n_pairs, int64_t cap, const int32_t* pair_img_dev, const int32_t* nq_dev,
+                    const int32_t* img_off_dev, int n_img, double ratio, const uint8_t* keep_dev, int32_t* edges_dev, void* stream);
+size_t sfm_track_components_ws_bytes(int64_t n_nodes, int64_t ne);
+int sfm_track_components(const int32_t* edges_dev, int64_t n_nodes, int64_t ne, int rounds, int resume, int32_t* labels_dev,
+                         int32_t* status_dev, void* ws_dev, size_t ws_bytes, void* stream);
+size_t sfm_track_build_ws_bytes(int64_t n_nodes);
+int sfm_track_build(const int32_t* labels_dev, const int32_t* img_off_dev, int64_t n_nodes, int n_img, int64_t min_len, int64_t max_len,
+                    int32_t* node_track_dev, int32_t* track_off_dev, int32_t* obs_node_dev, int32_t* counts_dev, void* ws_dev,
+                    size_t ws_bytes, void* stream);
+int sfm_track_triangulate(const int32_t* counts_dev, const int32_t* track_off_dev, const int32_t* obs_node_dev, const int32_t* img_off_dev,
+                          int n_img, const float* kp_dev, const double* P_dev, int64_t n_nodes, float* X_dev, float* err_dev,
+                          float* depth_dev, int32_t* flags_dev, float* max_err_dev, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

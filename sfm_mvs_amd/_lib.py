@@ -112,6 +112,12 @@ SIGNATURES = {
     "sfm_mesh_render_depth": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _i64, _i64, _vp, _vp]),
     "sfm_mesh_face_views": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _int, _i64, _i64, _vp, _f32, _vp, _vp, _vp]),
     "sfm_mesh_texture_fill": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _vp, _int, _int, _int, _vp, _vp]),
+    "sfm_match_edges": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _int, _f64, _vp, _vp, _vp]),
+    "sfm_track_components_ws_bytes": (_sz, [_i64, _i64]),
+    "sfm_track_components": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_build_ws_bytes": (_sz, [_i64]),
+    "sfm_track_build": (_int, [_vp, _vp, _i64, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_triangulate": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

@@ -1,0 +1,227 @@
+"""Feature tracks from all-pairs matches and their N-view triangulation (include/sfm_hip.h, "TRACKS"; docs/tracks.md).
+
+A node is `img_off[image] + keypoint`.  `match_edges` turns the device-resident match store of `sharded.match_pairs_sharded` into
+graph edges, `track_components` labels the connected components, `build_tracks` keeps the components that name no image twice and
+orders them, `triangulate_tracks` triangulates each from all its views.  All four take and return device tensors and never wait
+for the host; `run_tracks` composes them, reads the counts once and downloads once, and returns the points and observations in the
+form `ba.bundle_adjust_schur(cams, K, X, obs, cam_idx, pt_idx)` takes."""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import SfmHipError, check, on_device, ptr, require_cuda, stream_ptr
+from .mvs import _upload
+
+TRACK_ROUNDS = 6                # labelling rounds enqueued per call: twice the most any input of scripts/bench_tracks.py needed (docs/tracks.md §5)
+INT32_MAX = 2 ** 31 - 1
+
+
+def image_offsets(sizes, device):
+    """int32 [n_img + 1] device tensor of the node offsets of images with `sizes` keypoints."""
+    off = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum(np.asarray(sizes, np.int64), out=off[1:])
+    if off[-1] > INT32_MAX:
+        raise SfmHipError(f"tracks: {int(off[-1])} nodes exceed 2^31-1")
+    return _upload(off.astype(np.int32), device)
+
+
+def _i32(t, what, shape=None):
+    require_cuda(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise SfmHipError(f"tracks: {what} must be a contiguous int32 device tensor" + (f" of shape {tuple(shape)}" if shape is not None else ""))
+    return t
+
+
+def _offsets(img_off):
+    _i32(img_off, "img_off")
+    if img_off.dim() != 1 or img_off.numel() < 2:
+        raise SfmHipError("tracks: img_off must be int32 [n_img + 1] with n_img >= 1")
+    return int(img_off.numel()) - 1
+
+
+def match_edges(store, n_query, pairs, img_off, ratio=0.70, keep=None, out=None):
+    """sfm_match_edges: the Lowe survivors of store (int32 [n_pairs, 2, cap, 2]) as edges int32 [n_pairs * cap, 2], (-1, -1) in every
+    other slot.  n_query int32 [n_pairs] and pairs int32 [n_pairs, 2] are device tensors; keep: optional uint8 [n_pairs, cap], a
+    query must be non-zero there.  No host wait."""
+    require_cuda(store, keep)
+    if store.dtype != torch.int32 or store.dim() != 4 or store.shape[1] != 2 or store.shape[3] != 2 or not store.is_contiguous():
+        raise SfmHipError("match_edges: store must be a contiguous int32 [n_pairs, 2, cap, 2] device tensor")
+    n_pairs, cap, dev = int(store.shape[0]), int(store.shape[2]), store.device
+    n_img = _offsets(img_off)
+    _i32(n_query, "n_query", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    if keep is not None and (keep.dtype != torch.uint8 or tuple(keep.shape) != (n_pairs, cap) or not keep.is_contiguous()):
+        raise SfmHipError("match_edges: keep must be a contiguous uint8 [n_pairs, cap] device tensor")
+    edges = torch.empty((n_pairs * cap, 2), dtype=torch.int32, device=dev) if out is None else _i32(out, "edges", (n_pairs * cap, 2))
+    ne = n_pairs * cap
+    with on_device(dev):
+        check(_lib.lib().sfm_match_edges(ptr(store) if ne else None, n_pairs, cap, ptr(pairs) if ne else None, ptr(n_query) if ne else None,
+                                         ptr(img_off), n_img, float(ratio), ptr(keep) if ne else None, ptr(edges) if ne else None, stream_ptr()),
+              "sfm_match_edges")
+    return edges
+
+
+def track_components(edges, n_nodes, rounds=TRACK_ROUNDS, labels=None, status=None):
+    """sfm_track_components: label[u] = the smallest node id of u's component over the valid edges (both ends in 0..n_nodes-1 and
+    different), at most `rounds` (1..1024) rounds.  labels: an int32 [n_nodes] tensor an earlier call left, to continue from (updated
+    in place).  Returns (labels, status): status int32 [2] = (converged 0/1, rounds that lowered a label).  No host wait."""
+    from .ops import _workspace
+    require_cuda(edges)
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2 or not edges.is_contiguous():
+        raise SfmHipError("track_components: edges must be a contiguous [k, 2] int32 device tensor")
+    n, ne, dev = int(n_nodes), int(edges.shape[0]), edges.device
+    resume = labels is not None
+    if resume:
+        _i32(labels, "labels", (n,))
+    else:
+        labels = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev) if status is None else _i32(status, "status", (2,))
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_track_components_ws_bytes(max(n, 0), ne))
+    with on_device(dev):
+        check(L.sfm_track_components(ptr(edges) if ne else None, n, ne, int(rounds), int(resume), ptr(labels) if n > 0 else None, ptr(status),
+                                     ptr(ws), ws.numel(), stream_ptr()), "sfm_track_components")
+    return labels, status
+
+
+def build_tracks(labels, img_off, min_len=2, max_len=None, counts=None):
+    """sfm_track_build on converged labels: a component of >= 2 nodes is kept iff no two of its nodes lie in one image and
+    min_len <= size <= max_len.  Returns (node_track [N], track_off [N // 2 + 2], obs_node [N], counts [6]) int32 device tensors;
+    counts = (tracks T, observations, candidates, conflicting, longest kept, nodes in components of one node); T + 1 words of
+    track_off and counts[1] of obs_node are written, nothing past them.  No host wait."""
+    n_img = _offsets(img_off)
+    _i32(labels, "labels")
+    if labels.dim() != 1:
+        raise SfmHipError("build_tracks: labels must be int32 [N]")
+    n, dev = int(labels.numel()), labels.device
+    node_track = torch.empty(n, dtype=torch.int32, device=dev)
+    track_off = torch.empty(n // 2 + 2, dtype=torch.int32, device=dev)
+    obs_node = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(6, dtype=torch.int32, device=dev) if counts is None else _i32(counts, "counts", (6,))
+    build_tracks_into(labels, img_off, n_img, min_len, max_len, node_track, track_off, obs_node, counts)
+    return node_track, track_off, obs_node, counts
+
+
+def build_tracks_into(labels, img_off, n_img, min_len, max_len, node_track, track_off, obs_node, counts):
+    """build_tracks into buffers of the caller (the tests fill them with sentinels first)."""
+    from .ops import _workspace
+    n, dev = int(labels.numel()), labels.device
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_track_build_ws_bytes(n))
+    with on_device(dev):
+        check(L.sfm_track_build(ptr(labels) if n else None, ptr(img_off), n, n_img, int(min_len), INT32_MAX if max_len is None else int(max_len),
+                                ptr(node_track) if n else None, ptr(track_off), ptr(obs_node) if n else None, ptr(counts), ptr(ws),
+                                ws.numel(), stream_ptr()), "sfm_track_build")
+
+
+def triangulate_tracks(counts, track_off, obs_node, img_off, keypoints, P, out=None):
+    """sfm_track_triangulate: one lane per track, the counts read on the device.  keypoints float32 [N, 2] (all images concatenated),
+    P float64 [n_img, 12] or [n_img, 3, 4]: device tensors.  Returns (X [N // 2 + 1, 3] f32, err [N] f32, depth [N] f32,
+    flags [N // 2 + 1] i32, max_err [N // 2 + 1] f32), of which the first counts[0] / counts[1] rows are written.  No host wait."""
+    n_img = _offsets(img_off)
+    require_cuda(keypoints, P)
+    _i32(counts, "counts")
+    _i32(track_off, "track_off")
+    _i32(obs_node, "obs_node")
+    n, dev = int(obs_node.numel()), obs_node.device
+    if keypoints.dtype != torch.float32 or tuple(keypoints.shape) != (n, 2) or not keypoints.is_contiguous():
+        raise SfmHipError("triangulate_tracks: keypoints must be a contiguous float32 [N, 2] device tensor")
+    if P.dtype != torch.float64 or P.numel() != 12 * n_img or not P.is_contiguous():
+        raise SfmHipError("triangulate_tracks: P must be a contiguous float64 [n_img, 12] device tensor")
+    if counts.numel() < 2 or track_off.numel() < n // 2 + 2:
+        raise SfmHipError("triangulate_tracks: counts must hold (tracks, observations) and track_off N // 2 + 2 words")
+    cap = n // 2 + 1
+    if out is None:
+        out = (torch.empty((cap, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+               torch.empty(n, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+               torch.empty(cap, dtype=torch.float32, device=dev))
+    X, err, depth, flags, max_err = out
+    with on_device(dev):
+        check(_lib.lib().sfm_track_triangulate(ptr(counts), ptr(track_off), ptr(obs_node) if n else None, ptr(img_off), n_img,
+                                               ptr(keypoints) if n else None, ptr(P), n, ptr(X), ptr(err) if n else None,
+                                               ptr(depth) if n else None, ptr(flags), ptr(max_err), stream_ptr()), "sfm_track_triangulate")
+    return X, err, depth, flags, max_err
+
+
+def _scene_tensors(n_query, pairs, keypoints, P, dev):
+    sizes = [int(k.shape[0]) for k in keypoints]
+    img_off = image_offsets(sizes, dev)
+    kp = torch.cat([k.to(device=dev, dtype=torch.float32).reshape(-1, 2) for k in keypoints]).contiguous() if sizes else torch.empty((0, 2), device=dev)
+    nq = _upload(np.asarray(n_query, np.int32).reshape(-1), dev)
+    pr = _upload(np.asarray(pairs, np.int32).reshape(-1, 2), dev)
+    Pd = None if P is None else _upload(np.asarray(P, np.float64).reshape(len(sizes), 12), dev)
+    return img_off, kp, nq, pr, Pd, int(sum(sizes))
+
+
+def run_tracks(store, n_query, pairs, keypoints, P, ratio=0.70, keep=None, min_len=2, max_len=None, max_reproj=None, rounds=TRACK_ROUNDS):
+    """Match store -> tracks -> N-view points.  store, n_query, pairs as `sharded.match_pairs_sharded` returns and takes them;
+    keypoints: list over images of [n_i, 2] float32 device tensors; P: [n_img, 3, 4] float64 (host).  Keeps the tracks whose
+    triangulation has flags == 3 (every depth positive, a finite point) and, if max_reproj is given, a largest reprojection error
+    <= max_reproj.  Returns host arrays: points (T', 3) f32, obs (nobs', 2) f32, cam_idx, pt_idx (nobs',) i32, track_len (T',) i32,
+    counts (6,) as sfm_track_build writes them, status (2,) of the labelling.  Two host waits: the counts (with the status) and one
+    download; each batch of `rounds` rounds the labelling still needs after the first costs one more read of the status."""
+    dev = store.device
+    store = store.contiguous()
+    img_off, kp, nq, pr, Pd, n = _scene_tensors(n_query, pairs, keypoints, P, dev)
+    edges = match_edges(store, nq, pr, img_off, ratio, keep)
+    head = torch.empty(8, dtype=torch.int32, device=dev)
+    counts, status = head[:6], head[6:]
+    labels, lowered = None, 0
+    while True:
+        labels, _ = track_components(edges, n, rounds, labels, status)
+        node_track, track_off, obs_node, _ = build_tracks(labels, img_off, min_len, max_len, counts)
+        X, err, depth, flags, max_err = triangulate_tracks(counts, track_off, obs_node, img_off, kp, Pd)
+        host_head = head.cpu().numpy()                                # host wait 1: the counts and the status
+        lowered += int(host_head[7])
+        if host_head[6]:
+            break
+    T, nobs = int(host_head[0]), int(host_head[1])
+    nodes = obs_node[:nobs].long()
+    cam = (torch.searchsorted(img_off[:-1].contiguous(), obs_node[:nobs], right=True) - 1).to(torch.int32)
+    words = torch.cat([X[:T].reshape(-1).view(torch.int32), flags[:T], max_err[:T].view(torch.int32), track_off[:T + 1], cam,
+                       kp.index_select(0, nodes).reshape(-1).view(torch.int32)])
+    host = words.cpu().numpy()                                        # host wait 2: the one download
+    pos = np.cumsum([0, 3 * T, T, T, T + 1, nobs])
+    Xh = host[pos[0]:pos[1]].view(np.float32).reshape(T, 3)
+    fl, worst = host[pos[1]:pos[2]], host[pos[2]:pos[3]].view(np.float32)
+    off, camh = host[pos[3]:pos[4]].astype(np.int64), host[pos[4]:pos[5]]
+    obs = host[pos[5]:].view(np.float32).reshape(nobs, 2)
+    good = fl == 3
+    if max_reproj is not None:
+        with np.errstate(invalid="ignore"):
+            good &= worst <= np.float32(max_reproj)
+    length = np.diff(off)
+    track = np.repeat(np.arange(T), length)
+    sel = good[track]
+    new_id = np.cumsum(good) - 1
+    return dict(points=np.ascontiguousarray(Xh[good]), obs=np.ascontiguousarray(obs[sel]), cam_idx=np.ascontiguousarray(camh[sel]),
+                pt_idx=new_id[track[sel]].astype(np.int32), track_len=length[good].astype(np.int32), counts=host_head[:6].copy(),
+                status=np.array([int(host_head[6]), lowered], np.int32))
+
+
+def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70):
+    """The per-query inlier masks of `sharded.HipVerifyEngine`'s two stages (isfm.py:73-94: essential-matrix RANSAC on the Lowe
+    survivors, then the cheirality vote of recoverPose on its inliers) as the `keep` tensor of `match_edges`: uint8 [n_pairs, cap],
+    1 at the queries that survive both.  A pair with fewer than five survivors or without an essential matrix keeps nothing.
+    Waits for the host as the engine does (per pair)."""
+    from . import ops, ransac
+    dev = store.device
+    n_pairs, cap = int(store.shape[0]), int(store.shape[2])
+    keep = torch.zeros((n_pairs, cap), dtype=torch.uint8, device=dev)
+    for p, (i, j) in enumerate(pairs):
+        nq = int(n_query[p])
+        block = store[p]
+        out_q, out_t, count = ops.ratio_compact(block[0, :nq], block[1, :nq].view(torch.float32), ratio)
+        pts0, pts1 = ops.gather_matches(keypoints[i], keypoints[j], out_q, out_t, count)
+        m = int(count.item())
+        if m < 5:
+            continue
+        pts0, pts1 = pts0[:m], pts1[:m]
+        E, mask = ransac.find_essential_mat(pts0, pts1, K, 0.999, 0.4, return_device_mask=True)
+        if E is None:
+            continue
+        first = ops.mask_indices(mask).long()
+        _, _, _, mask2 = ransac.recover_pose(E[:3], pts0[first], pts1[first], K, return_device_mask=True)
+        second = ops.mask_indices(mask2, nonzero=True).long()
+        keep[p].index_fill_(0, out_q[:m].long()[first[second]], 1)
+    return keep
