@@ -4,7 +4,7 @@ with every query's own lanes walking its own list (trip count: the longest of th
 the wave's lanes.  No GPU: numpy only.  usage: python scripts/q8_pass_model.py [nq = 1500] [nt = 10000] [seed = 0]
 
 The model follows the kernel: one 8-bit grid per pair (lo, s from sixteen sampled rows per side), D = sum (k_q - k_t)^2, E =
-||q - q^|| + max_t ||t - t^|| in units of s, records of eight train rows (row 16 e + 8 (r >> 2) + 4 h + (r & 3) of a 32-row tile),
+||q - q^|| + max_t ||t - t^|| in units of s, records of eight ADJACENT train rows (rows 16 e + 8 h + r, r = 0 .. 7, of a 32-row tile),
 per (substream, half-wave h) the three smallest record keys (key = (min D of the record - cq) >> 1), the selection bound U from the
 second smallest key, R and Dlim by the kernel's float32 formulas, records listed up to Dlim, rows evaluated in float32 when
 D <= Dlim, a substream certified when its third key's lower bound exceeds the second distance.  base = 0, cq = 0 (they cancel)."""
@@ -36,8 +36,8 @@ tiles = (nt + 31) // 32
 BIG = np.int32(1 << 30)
 Dp = np.full((nq, tiles * 32), BIG, np.int32)
 Dp[:, :nt] = D
-# row of a tile = 16 e + 8 r2 + 4 h + r1: a record is (tile, e, h)
-recmin = Dp.reshape(nq, tiles, 2, 2, 2, 4).min(axis=(3, 5))      # [query, tile, e, h]
+# row of a tile = 16 e + 8 h + r: a record is (tile, e, h)
+recmin = Dp.reshape(nq, tiles, 2, 2, 8).min(axis=4)               # [query, tile, e, h]
 dist = lambda i, rows: np.sqrt(((q[i][None, :].astype(np.float64) - t[rows].astype(np.float64)) ** 2).sum(1))
 
 
@@ -70,7 +70,7 @@ def model(L):
         pi, ki = np.nonzero(listed)
         col = top[i][pi, ki]
         tl, ee, hh = tile_of[pi, col], e_of[pi, col], h_of[pi, col]
-        rows = (tl[:, None] * 32 + 16 * ee[:, None] + 4 * hh[:, None] + np.array([0, 1, 2, 3, 8, 9, 10, 11])[None, :]).ravel()
+        rows = (tl[:, None] * 32 + 16 * ee[:, None] + 8 * hh[:, None] + np.arange(8)[None, :]).ravel()
         rows = rows[rows < nt]
         rows = rows[D[i, rows] <= dlim]
         nrow[i] = len(rows)

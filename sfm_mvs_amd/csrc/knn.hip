@@ -2296,8 +2296,9 @@ __device__ __forceinline__ void filter_q4_body(
 //     a wave owns EIGHT 32-query groups (B fragments: 8 x 4 x 4 = 128 AGPRs), every train fragment (one 1 KiB load) feeds 8
 //     MFMAs — with 4 groups the four waves' fragment loads (20 KiB per tile through the CU's 64 B/clk L1 path) cost 34 of a
 //     tile-group's 128 pipe cycles (scripts/ubench/filter_i8.hip, profiles/r04_ubench_filter_i8_skeleton.txt);
-//   * a candidate record is HALF of a lane's 16 accumulator registers — registers 8 e .. 8 e + 7 = the 8 train rows
-//     16 e + 8 (r >> 2) + 4 h + (r & 3) of a tile — so the epilogue is 2 x (4 min3 / min + 1 pack + 3 insert) = 16 VALU per group
+//   * a candidate record is HALF of a lane's 16 accumulator registers — registers 8 e .. 8 e + 7 = the 8 ADJACENT train rows
+//     16 e + 8 h + (r & 7) of a tile (the train fragments are loaded through voff_t below: one 128-byte line per k-chunk and
+//     record for the refine kernel) — so the epilogue is 2 x (4 min3 / min + 1 pack + 3 insert) = 16 VALU per group
 //     and tile, FOUR per MFMA gap (quads: six, more than a wave alone on its SIMD hides; whole-lane records: three, but the
 //     refine kernel then reads 16 rows per record — its L1 traffic doubled and it lost more than the filter gained);
 //     the key's low 8 bits are (tile inside a 128-tile substream) << 1 | e;
@@ -2335,7 +2336,13 @@ __device__ __forceinline__ void filter_i8_body(
     const int bid = (G & 7) == 0 ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;   // XCD-aware order
     const int64_t u_end = wg_begin[bid + 1];
     int64_t u = wg_begin[bid];
-    const int voff = lane * 16;
+    // The TRAIN fragments are loaded with image bits 2 and 3 of the row slot swapped: A-operand slot jj takes the image's row
+    // sigma(jj), so accumulator register r of half-wave h (product row 8 (r >> 2) + 4 h + (r & 3)) holds tile row
+    // 16 (r >> 3) + 8 h + (r & 7) and a record (registers 8 e .. 8 e + 7) is the eight ADJACENT rows 16 e + 8 h .. + 7: 128
+    // contiguous, line-aligned bytes per k-chunk of the image for the refine kernel's row loads.  Bits 0-1 stay: a wave-level
+    // load still covers the same 1 KiB in the same 64-byte quads.  The query fragments keep lane * 16 (column jj = query jj).
+    auto train_off = [](int l) { return ((l & ~12) | ((l & 4) << 1) | ((l & 8) >> 1)) * 16; };
+    const int voff_t = train_off(lane);
     const int qtiles = nq_pad >> 5;
 
     while (u < u_end) {
@@ -2360,7 +2367,7 @@ __device__ __forceinline__ void filter_i8_body(
         auto load_frag = [&](int s_, int f, int tile_, bool live, bool in_loop = false) {
             if ((ABL & 1) && in_loop) return;
             const int tile = live ? tile_ : t_end - 1;
-            fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff, __builtin_amdgcn_readfirstlane(tile * kI8TileBytes + f * 1024), 0);
+            fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t, __builtin_amdgcn_readfirstlane(tile * kI8TileBytes + f * 1024), 0);
         };
 #pragma unroll
         for (int d = 0; d < D; ++d) {
@@ -2372,11 +2379,17 @@ __device__ __forceinline__ void filter_i8_body(
         u32x4 bq[NG][4], bi;
         {
             i32x4 tmp[NG][4];
+            // lane * 16 again, from voff_t (bits 6 and 7 swapped back) behind an opaque copy: formed from `lane` it is hoisted out
+            // of the segment loop and stays live through the tile loop, one register more than the parent's single offset
+            int voff_q = voff_t;
+            asm volatile("" : "+v"(voff_q));
+            const int sw = (voff_q ^ (voff_q >> 1)) & 64;                      // (64: an inline constant, no register)
+            voff_q ^= sw | (sw << 1);
 #pragma unroll
             for (int g = 0; g < NG; ++g)
 #pragma unroll
                 for (int f = 0; f < 4; ++f)
-                    tmp[g][f] = __builtin_amdgcn_raw_buffer_load_b128(qrs, voff, __builtin_amdgcn_readfirstlane((qg0 + g) * kI8QTileBytes + f * 1024), 0);
+                    tmp[g][f] = __builtin_amdgcn_raw_buffer_load_b128(qrs, voff_q, __builtin_amdgcn_readfirstlane((qg0 + g) * kI8QTileBytes + f * 1024), 0);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g < NG; ++g)
@@ -2424,7 +2437,7 @@ __device__ __forceinline__ void filter_i8_body(
         const int nrem = nt & 31;                                             // real rows of the partial tile (0: none is partial)
         auto mask_tail = [&](i32x16& a) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = 8 * (r >> 2) + 4 * h + (r & 3) >= nrem ? 0x7FFFFF : a[r];
+            for (int r = 0; r < 16; ++r) a[r] = 16 * (r >> 3) + 8 * h + (r & 7) >= nrem ? 0x7FFFFF : a[r];
         };
         // one group's epilogue (16 VALU) in four pieces, one per MFMA gap of a k-step.  The two 8-register records' min trees are
         // interleaved (a wave alone on its SIMD stalls on every dependent vector-ALU pair: independent neighbours fill the slots)
@@ -2707,7 +2720,8 @@ constexpr int kQualCap = 144;    // exact-evaluation list per query (a chunk of 
 // ---------------------------------------------------------------- refine, exact-integer body
 // Sixteen lanes per query as above, but everything is integer and every wave is on its own (no workgroup barrier):
 //   records   three packed keys (acc << 8 | tile-in-substream << 1 | e) per stream; a record = the 8 train rows
-//             16 e + 8 (r >> 2) + 4 h + (r & 3), r = 0 .. 7, of a tile (half of a lane's accumulator registers in the filter)
+//             16 e + 8 h + r, r = 0 .. 7, of a tile (half of a lane's accumulator registers in the filter, whose train loads
+//             swap slot bits 2 and 3): 128 contiguous, line-aligned bytes per k-chunk of the image — one line per load instruction
 //   select    a(2) = the second smallest record score; a row of the exact top-2 (ties and float32 square roots that collide
 //             included) sits in a record with score <= a(2) + 1:  two distinct rows with d^2 <= U = c_q - 128 + 2 (a(2) + base) + 1
 //             exist, so d2^2 <= U, and a row with d^2 <= d2^2 + 2 has acc <= a(2) + 1.5
@@ -2822,7 +2836,7 @@ __device__ __forceinline__ void refine_i8_body(
     // one row per lane: register r = sl & 7 of record (tile, half-wave hh, register half e) -> exact d^2, inserted under (sqrtf, index)
     auto eval_row = [&](int tile, int hh, int e, bool live, int qslot, int cqv, Best2I& acc2) {
         const int r = sl & 7;
-        const int jr = 16 * e + 8 * (r >> 2) + 4 * hh + (r & 3);
+        const int jr = 16 * e + 8 * hh + r;
         const int row = tile * kTileT + jr;
         const unsigned char* tp = ti8 + (int64_t)tile * kI8TileBytes + (jr << 4);
         uint4 tv[8];
@@ -3126,7 +3140,7 @@ __device__ __forceinline__ void refine_q8_body(
     __builtin_amdgcn_wave_barrier();
     // exact D of one row per lane: register r of record (tile, half-wave hh, register half e) against the bytes of query slot `qslot`
     auto int_row = [&](int tile, int hh, int e, int r, int qslot, int cqv, int& row) -> int {
-        const int jr = 16 * e + 8 * (r >> 2) + 4 * hh + (r & 3);
+        const int jr = 16 * e + 8 * hh + r;
         row = tile * kTileT + jr;
         const unsigned char* tp = ti8 + (int64_t)tile * kI8TileBytes + (jr << 4);
         uint4 tv[8];
