@@ -1024,6 +1024,11 @@ int sfm_debug_knn_prep_blocks(int n);
  * lists over its eight 8-lane groups (the default, on != 0).  Results do not depend on it (tests/test_gpu_knn_refine_pooled.py); it
  * also serves same-box timing comparisons. */
 int sfm_debug_knn_refine_pooled(int on);
+/* Test hook: every following plan of the integer bodies' filter (exact-integer and quantised: stats[3] = 4 / 5) gets at most `n`
+ * (1 .. 256) workgroups instead of min(256, units); 0 restores the rule.  With few workgroups a segment spans several substreams at
+ * small sizes (the key flush inside the tile loop, tests/test_gpu_knn_flush.py).  The count sizes the workspace: call it BEFORE the
+ * *_ws_bytes query and keep it until the launch.  Results do not depend on it. */
+int sfm_debug_knn_filter_workgroups(int n);
 int sfm_profile_read(int slot, double* total_ms_host, int64_t* launches_host);
 /* How often library calls of this process have WAITED for the device so far (cumulative; the RANSAC entry points read the
  * hypothesis scores back chunk by chunk, the Schur solver its convergence scalars).  Diagnostics: bench.py reports the

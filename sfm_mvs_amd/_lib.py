@@ -128,6 +128,7 @@ SIGNATURES = {
     "sfm_debug_knn_prep_general": (_int, [_int]),
     "sfm_debug_knn_refine_pooled": (_int, [_int]),
     "sfm_debug_knn_prep_blocks": (_int, [_int]),
+    "sfm_debug_knn_filter_workgroups": (_int, [_int]),
     "sfm_profile_read": (_int, [_int, _c.POINTER(_f64), _c.POINTER(_i64)]),
 }
 

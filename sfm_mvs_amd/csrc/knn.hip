@@ -159,6 +159,7 @@ constexpr int dev_env_int(const char*, int dflt) { return dflt; }
 const int g_seg_cost = dev_env_int("SFM_KNN_SEGCOST", kSegCostTiles);
 const int g_q8 = dev_env_int("SFM_KNN_Q8", 1);                  // 0 = kFilterAuto never quantises (= kFilterNoQuant)
 const int g_seg_cost_q4 = dev_env_int("SFM_KNN_SEGCOST_Q4", 5); // q4 kernel: a segment's prologue in tile-steps
+int g_filter_wgs = 0;           // test hook: cap of the i8 plans' workgroup count (0: the rule) — a workgroup spans several substreams at small sizes
 
 // One workgroup fills the partition tables the filter / refine kernels read: begin[G+1], and per query row block the
 // first and last block that touches it.
@@ -215,7 +216,7 @@ Plan make_plan_uncached(int64_t nq, int64_t nt, int B, int filter);
 Plan make_plan(int64_t nq, int64_t nt, int B, int filter) {
     struct Entry {
         int64_t nq = -1, nt = -1;
-        int B = -1, mode = -1, seg = -1;
+        int B = -1, mode = -1, seg = -1, wgs = -1;
         unsigned long long used = 0;
         Plan plan;
     };
@@ -225,14 +226,14 @@ Plan make_plan(int64_t nq, int64_t nt, int B, int filter) {
     std::lock_guard<std::mutex> lk(mu);
     Entry* victim = &cache[0];
     for (Entry& e : cache) {
-        if (e.nq == nq && e.nt == nt && e.B == B && e.mode == filter && e.seg == g_seg_cost) {
+        if (e.nq == nq && e.nt == nt && e.B == B && e.mode == filter && e.seg == g_seg_cost && e.wgs == g_filter_wgs) {
             e.used = ++tick;
             return e.plan;
         }
         if (e.used < victim->used) victim = &e;
     }
     victim->plan = make_plan_uncached(nq, nt, B, filter);
-    victim->nq = nq; victim->nt = nt; victim->B = B; victim->mode = filter; victim->seg = g_seg_cost;
+    victim->nq = nq; victim->nt = nt; victim->B = B; victim->mode = filter; victim->seg = g_seg_cost; victim->wgs = g_filter_wgs;
     victim->used = ++tick;
     return victim->plan;
 }
@@ -262,6 +263,7 @@ Plan make_plan_uncached(int64_t nq, int64_t nt, int B, int filter) {
     static const int env_res = dev_env_int("SFM_KNN_RESIDENT", 0);
     int64_t g = (env_res > 0 ? env_res : kResidentWaves / p.qg) / p.waves;
     if (i8plan) g = 256;                       // (one workgroup per CU, as the q4 bodies: they are bodies of one kernel)
+    if (i8plan && g_filter_wgs > 0 && g > g_filter_wgs) g = g_filter_wgs;   // (test hook: long segments at small sizes)
     if (g > p.units) g = p.units;
     if (g > (int64_t)p.n_rb * (kMaxSlots - 2)) g = (int64_t)p.n_rb * (kMaxSlots - 2);
     if (g < 1) g = 1;
@@ -2358,9 +2360,6 @@ __device__ __forceinline__ void filter_i8_body(
         const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc((void*)(qi8 + pb * s_qi8), 0, qtiles * kI8QTileBytes, 0x00020000);
         const int qg0 = rbl * (kI8Rows / 32) + wave * NG;                      // first 32-query tile of this wave
         const int qloc0 = wave * NG * 32 + j;                                  // query inside the row block; group g adds 32 g
-        bool qok[NG];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) qok[g] = qg0 * 32 + j + 32 * g < nq;
 
         // ---- train fragments of the first D tiles (init fragment first: it is consumed first), then the query fragments
         i32x4 fr[D][5];
@@ -2406,15 +2405,21 @@ __device__ __forceinline__ void filter_i8_body(
         int sub = 0, sub_t0 = t_begin;
         auto flush = [&](int sb, int st0, int st1) {
             // cold: once per substream.  keys[((rbl * nstr + stream) * 2 + h) * 1024 + query-in-block][4]: the stream's three keys
-            // of a query as ONE 16-byte store (the fourth word is padding) — a flush is 8 stores per lane instead of 24, and the
-            // fragment wait that follows has to sit their completion out (stores and loads share vmcnt): 87.2 -> 84.0 us per batch
-            // of 8 with 32-tile substreams (measured with a one-store-per-group build before the layout was changed)
-            int ql = qloc0;
-            asm volatile("" : "+v"(ql));
-            const int64_t ob = ((int64_t)(rbl * nstr + sbase + sb) * 2 + h) * kI8Rows * 4;
+            // of a query as ONE 16-byte store (the fourth word is padding), 8 stores per lane and flush.  Stores and loads share
+            // vmcnt, so every wait for a train fragment that hipcc cannot PROVE older than these stores sits their completion out:
+            // the flush therefore has a round of its own (see the round loop) and is as short as it can be made —
+            //   * all eight slots are stored, a dead query's too (the array is padded to kI8Rows queries per row block, the refine
+            //     kernel never reads a dead query's slot): no exec mask per group, no branch between the stores;
+            //   * the slot (2 x 1024 x 16 bytes) is addressed through a buffer resource of its own: a scalar 64-bit base, ONE
+            //     per-lane offset and the immediates 512 g — no 64-bit vector arithmetic, and no limit on the key array's size
+            //     (the resource spans one slot, never the pair's array).
+            int vo = qloc0 * 16 + h * (kI8Rows * 16);
+            asm volatile("" : "+v"(vo));
+            const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(keys + (int64_t)(rbl * nstr + sbase + sb) * (2 * kI8Rows * 4)), 0, 2 * kI8Rows * 16, 0x00020000);
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
-                if (qok[g]) *reinterpret_cast<int4*>(keys + ob + (int64_t)(ql + 32 * g) * 4) = make_int4(k0[g], k1[g], k2[g], INT_MAX);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{(unsigned)k0[g], (unsigned)k1[g], (unsigned)k2[g], (unsigned)INT_MAX}, krs, vo + 512 * g, 0, 0);
                 k0[g] = k1[g] = k2[g] = INT_MAX;
             }
             if (threadIdx.x == 0) {                                            // the stream's tile range, for the refine kernel's decode / rescan
@@ -2449,9 +2454,13 @@ __device__ __forceinline__ void filter_i8_body(
             else if (piece == 1) { m0 = imin3(m0, m1, a[6]); n0 = imin3(n0, n1, a[14]); m0 = min(m0, a[7]); n0 = min(n0, a[15]); }
             else if (piece == 2) { key = key_pack_i8(m0, seq); key2 = key_pack_i8(n0, seq | 1); key_put(key, e0, e1, e2); }
             else key_put(key2, e0, e1, e2);
+            // the keys' updates stay in THIS gap (no instruction): with no flush between a round's tiles nothing reads the keys before
+            // the round's end, and hipcc sank the min / med3 triples of a whole round into the loop latch, behind its last three MFMAs
+            if (piece >= 2) asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2));
         };
-        auto tile = [&](int t, auto slot_c) {
+        auto tile = [&](int t, auto slot_c, auto flush_c) {
             constexpr int S = decltype(slot_c)::value;
+            constexpr int FL = decltype(flush_c)::value;            // 0: no boundary at t (no test, no store); 1: a boundary at t; 2: tested
             const bool more = t + D < t_end;
             const int seq_prev = __builtin_amdgcn_readfirstlane(max((t - 1) - sub_t0, 0) << 1);
             const bool part_cur = nrem != 0 && t + 1 == tiles;      // (wave-uniform) t is the train image's last, partial tile; its second-half groups' epilogue is the tail's
@@ -2469,7 +2478,7 @@ __device__ __forceinline__ void filter_i8_body(
                 }
             }
             // ---- substream boundary: every group's keys now cover exactly the tiles before t
-            if (t - sub_t0 == sub_tiles) {
+            if (FL == 1 || (FL == 2 && t - sub_t0 == sub_tiles)) {
                 flush(sub, sub_t0, t);
                 ++sub;
                 sub_t0 = t;
@@ -2494,13 +2503,34 @@ __device__ __forceinline__ void filter_i8_body(
                 load_frag(S, st, t + D, more, true);
             }
         };
-        // whole rounds of D tiles, the remainder after the loop (see the fp16 body: hipcc's waitcnt merge at the back edge)
+        // whole rounds of D tiles, the remainder after the loop (see the fp16 body: hipcc's waitcnt merge at the back edge).
+        // sub_tiles is even (32 or 128) and D = 2: a substream boundary inside the rounds always falls on a round's slot-0 tile.
+        // The steady round carries neither the boundary test nor a store: its loop runs to the next boundary (or the last whole
+        // round).  The boundary round is a copy of its own — straight-line code from the flush's stores through the next tile's
+        // fragment waits, so hipcc counts the stores into those waits' immediates (the fragments waited for are OLDER than the
+        // stores: vmcnt(8 + 9) .. instead of vmcnt(8) ..) and the first wait that covers the stores is the one for the fragments
+        // loaded after them, a whole tile later.  With the flush as a branch inside tile() the two paths' counters were merged at
+        // the join and the wave sat out its stores 17 MFMAs after issuing them, 3 to 5 times per workgroup.
+        // (The asm comments keep the two rounds' identical second tiles from being tail-merged into one block BEFORE the wait
+        // counts are inserted, which would bring the merged immediates back.)
+        constexpr std::integral_constant<int, 0> c0{};
+        constexpr std::integral_constant<int, 1> c1{};
+        constexpr std::integral_constant<int, 2> c2{};
         int t = t_begin;
-        for (; t + D <= t_end; t += D) {
-            tile(t, std::integral_constant<int, 0>{});
-            tile(t + 1, std::integral_constant<int, 1>{});
+        for (;;) {
+            const int t_stop = __builtin_amdgcn_readfirstlane(min(sub_t0 + sub_tiles, t_end - (D - 1)));   // (even distance from t)
+            for (; t < t_stop; t += D) {
+                tile(t, c0, c0);
+                tile(t + 1, c1, c0);
+                asm volatile("; steady round" ::: "memory");
+            }
+            if (t + D > t_end) break;
+            tile(t, c0, c1);                                                 // t - sub_t0 == sub_tiles
+            tile(t + 1, c1, c0);
+            asm volatile("; boundary round" ::: "memory");
+            t += D;
         }
-        if (t < t_end) tile(t, std::integral_constant<int, 0>{});
+        if (t < t_end) tile(t, c0, c2);                                      // (33, 65, 129 tiles: the boundary falls on the remainder tile)
         // epilogue of the last tile's groups P .. NG-1 (the MFMAs that completed them were the last instructions issued)
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
         if (t_end > t_begin) {
@@ -4409,6 +4439,12 @@ extern "C" int sfm_debug_knn_prep_general(int on) {
 extern "C" int sfm_debug_knn_prep_blocks(int n) {
     SFM_CHECK_ARG(n >= 0 && n <= kNormBlocks, "sfm_debug_knn_prep_blocks: 0 (the rule) or 1 .. %d workgroups per pair (got %d)", kNormBlocks, n);
     g_prep_blocks = n;
+    return SFM_OK;
+}
+
+extern "C" int sfm_debug_knn_filter_workgroups(int n) {
+    SFM_CHECK_ARG(n >= 0 && n <= 256, "sfm_debug_knn_filter_workgroups: 0 (the rule) or 1 .. 256 workgroups of the integer bodies' filter (got %d)", n);
+    g_filter_wgs = n;
     return SFM_OK;
 }
 

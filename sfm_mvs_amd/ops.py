@@ -869,6 +869,12 @@ def knn_mfma_selftest_result(device="cuda"):
     return worst.value, scale.value
 
 
+def debug_knn_filter_workgroups(n):
+    """Test hook (sfm_debug_knn_filter_workgroups): at most n (1 .. 256) workgroups for the integer bodies' filter, 0 = the rule.
+    It sizes the workspace: set it before a matcher is built and keep it while that matcher runs."""
+    check(_lib.lib().sfm_debug_knn_filter_workgroups(int(n)), "sfm_debug_knn_filter_workgroups")
+
+
 def profile_enable(on=True):
     """False / True, or an int n > 1: the knn filter kernel is launched n times inside each event pair."""
     check(_lib.lib().sfm_profile_enable(int(on)), "sfm_profile_enable")
