@@ -2319,11 +2319,9 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 // reading them as SrcC (no hardware interlock: results of a whole query group went wrong, found by tests/test_gpu_knn_i8.py).
 #define SFM_MFMA_I8_REINIT(acc, a, b) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "+v"(acc) : "v"(a), "a"(b))
 
-__device__ __forceinline__ int key_pack_i8(int m, int seq /*wave-uniform*/) {
-    int key;
-    asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(key) : "v"(m), "s"(seq));
-    return key;
-}
+// (plain C++: hipcc emits the single v_lshl_or_b32 with the scalar seq.  As an asm statement the pack DEFINED a register of an
+// inline asm, and hipcc's hazard recogniser put an s_nop before the first compiler-emitted VALU that read it.)
+__device__ __forceinline__ int key_pack_i8(int m, int seq /*wave-uniform*/) { return (m << 8) | seq; }
 __device__ __forceinline__ int imin3(int a, int b, int c) { return min(min(a, b), c); }   // v_min3_i32
 
 template <int ABL>
@@ -2447,23 +2445,46 @@ __device__ __forceinline__ void filter_i8_body(
         // one group's epilogue (16 VALU) in four pieces, one per MFMA gap of a k-step.  The two 8-register records' min trees are
         // interleaved (a wave alone on its SIMD stalls on every dependent vector-ALU pair: independent neighbours fill the slots)
         int m0 = 0, m1 = 0, n0 = 0, n1 = 0, key = 0, key2 = 0;
-        auto epi = [&](int piece, i32x16& a, int seq /*(tile in substream) << 1*/, int& e0, int& e1, int& e2, bool partial) {
+        // Four pieces of four VALU each: every MFMA gap of a k-step carries the same load.  seq1 = seq | 1 (the second record's key).
+        auto epi = [&](int piece, i32x16& a, int seq /*(tile in substream) << 1*/, int seq1, int& e0, int& e1, int& e2, bool partial) {
             if (ABL & 2) { if (piece == 0) e0 = min(e0, a[0] + a[15]); return; }
             if (piece == 0 && partial) mask_tail(a);
             if (piece == 0) { m0 = imin3(a[0], a[1], a[2]); n0 = imin3(a[8], a[9], a[10]); m1 = imin3(a[3], a[4], a[5]); n1 = imin3(a[11], a[12], a[13]); }
             else if (piece == 1) { m0 = imin3(m0, m1, a[6]); n0 = imin3(n0, n1, a[14]); m0 = min(m0, a[7]); n0 = min(n0, a[15]); }
-            else if (piece == 2) { key = key_pack_i8(m0, seq); key2 = key_pack_i8(n0, seq | 1); key_put(key, e0, e1, e2); }
-            else key_put(key2, e0, e1, e2);
+            else if (piece == 2) { key = key_pack_i8(m0, seq); key_put(key, e0, e1, e2); }
+            else { key2 = key_pack_i8(n0, seq1); key_put(key2, e0, e1, e2); }
             // the keys' updates stay in THIS gap (no instruction): with no flush between a round's tiles nothing reads the keys before
-            // the round's end, and hipcc sank the min / med3 triples of a whole round into the loop latch, behind its last three MFMAs
-            if (piece >= 2) asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2));
+            // the round's end, and hipcc sank the min / med3 triples of a whole round into the loop latch, behind its last three MFMAs.
+            // The pin only READS the keys: as "+v" it defined them, and hipcc's hazard recogniser put an s_nop before the next
+            // compiler-emitted VALU that read a register an inline asm had written.
+            if (piece >= 2) asm volatile("" :: "v"(e0), "v"(e1), "v"(e2));
         };
-        auto tile = [&](int t, auto slot_c, auto flush_c) {
+        // A unit is one MFMA and its piece between two scheduling barriers; hipcc orders the asm MFMA freely against the piece.
+        // With a barrier between the two (MFMA first: every gap of the steady round <= 6 single-issue instructions, the round
+        // MFMA-paced in the issue model) the filter ALONE gained what this build gains on the parent, each on its own box (4.4 %
+        // and 3.9 %: the clock inside the kernel falls by a tenth either way), and the step ran 3.4 % SLOWER than the parent's
+        // where this build's runs 1.3 % faster, on one box: the other launch set's refine beside the paced filter took 163 us
+        // instead of 114 (docs/knn.md, docs/not_kept.md).  What pays in the step is the work taken out of the round.
+        // Scalars of the tile loop are carried and advanced by additions, each written into the gap that has room for it (a gap
+        // hides five to six single-issue instructions beside its MFMA, the four of a piece included):
+        //   ld_off  byte offset of the tile whose fragments tile t refills, min(t + D, t_end - 1) tiles into the image;
+        //   sq, sq1 (tile in substream) << 1 of the tile before t (0 before a segment's first) and sq | 1;  sq_n: the same of t.
+        const int ld_last = __builtin_amdgcn_readfirstlane((t_end - 1) * kI8TileBytes);
+        int ld_off = __builtin_amdgcn_readfirstlane(min(t_begin + D - 1, t_end - 1) * kI8TileBytes);
+        int sq = 0, sq1 = 1, sq_n = 0;
+        auto load_next = [&](int s_, int f, int off, int off4) {
+            if (ABL & 1) return;
+            // (fragments 0 .. 3 through the instruction's immediate offset: no scalar addition per load)
+            if (f < 4) fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t + f * 1024, off, 0);
+            else fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t, off4, 0);
+        };
+        auto tile = [&](int t, auto slot_c, auto flush_c, auto tail_c) {
             constexpr int S = decltype(slot_c)::value;
             constexpr int FL = decltype(flush_c)::value;            // 0: no boundary at t (no test, no store); 1: a boundary at t; 2: tested
-            const bool more = t + D < t_end;
-            const int seq_prev = __builtin_amdgcn_readfirstlane(max((t - 1) - sub_t0, 0) << 1);
-            const bool part_cur = nrem != 0 && t + 1 == tiles;      // (wave-uniform) t is the train image's last, partial tile; its second-half groups' epilogue is the tail's
+            constexpr int TL = decltype(tail_c)::value;             // 0: t is never the train image's partial last tile (no test, no mask code); 2: tested
+            const int seq_prev = sq, seq_prev1 = sq1;
+            const bool part_cur = TL == 2 && nrem != 0 && t + 1 == tiles;   // (wave-uniform) t is the train image's last, partial tile; its second-half groups' epilogue is the tail's
+            int off4 = 0;
             // ---- phase A: chains of groups 0 .. 3; k-step st carries the epilogue of group P + st (previous tile)
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
@@ -2473,21 +2494,37 @@ __device__ __forceinline__ void filter_i8_body(
                     __builtin_amdgcn_sched_barrier(0);
                     if (st == 0) SFM_MFMA_I8_C(acc[g], a, bq[g][st], cinit);
                     else SFM_MFMA_I8(acc[g], a, bq[g][st]);
-                    epi(g, acc[P + st], seq_prev, k0[P + st], k1[P + st], k2[P + st], false);
+                    epi(g, acc[P + st], seq_prev, seq_prev1, k0[P + st], k1[P + st], k2[P + st], false);
+                    if (st == 0 && g == 1) ld_off = __builtin_amdgcn_readfirstlane(min(ld_off + kI8TileBytes, ld_last));
+                    if (st == 1 && g == 1) off4 = __builtin_amdgcn_readfirstlane(ld_off + 4 * 1024);
+                    if (st == 2 && g == 1 && FL == 0) { sq = sq_n; sq1 = __builtin_amdgcn_readfirstlane(sq_n | 1); }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             // ---- substream boundary: every group's keys now cover exactly the tiles before t
-            if (FL == 1 || (FL == 2 && t - sub_t0 == sub_tiles)) {
-                flush(sub, sub_t0, t);
-                ++sub;
-                sub_t0 = t;
+            if (FL != 0) {
+                if (FL == 1 || t - sub_t0 == sub_tiles) {
+                    flush(sub, sub_t0, t);
+                    ++sub;
+                    sub_t0 = t;
+                    sq_n = 0;
+                }
+                sq = sq_n;
+                sq1 = __builtin_amdgcn_readfirstlane(sq_n | 1);
             }
-            const int seq_cur = __builtin_amdgcn_readfirstlane((t - sub_t0) << 1);
-            // ---- phase B: chains of groups 4 .. 7; epilogue of groups 0 .. 3 (this tile); the fragments die one by one and are
-            // refilled for tile t + D; the NEXT tile's init MFMA two MFMAs after the last reader of the current values
+            const int seq_cur = sq, seq_cur1 = sq1;
+            // ---- phase B: chains of groups 4 .. 7 and the NEXT tile's init MFMA (two MFMAs after the last reader of the current
+            // values): 17 MFMAs.  The 16 pieces of the epilogue of groups 0 .. 3 (this tile: complete since phase A) follow the
+            // first 16, so the gap behind the last MFMA — the one that crosses into the next tile, or the back edge — holds the
+            // last fragment load, the next tile's first wait and the loop control only.  The fragments die one by one and are
+            // refilled for tile t + D.
             __builtin_amdgcn_sched_barrier(0);
-            load_frag(S, 4, t + D, more, true);
+            load_next(S, 4, ld_off, off4);
+            int n = 0;                                             // MFMAs of this phase so far
+            auto piece_b = [&]() {
+                if (n < 16) epi(n & 3, acc[n >> 2], seq_cur, seq_cur1, k0[n >> 2], k1[n >> 2], k2[n >> 2], part_cur);
+                ++n;
+            };
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
                 const u32x4 a = __builtin_bit_cast(u32x4, fr[S][st]);
@@ -2496,11 +2533,17 @@ __device__ __forceinline__ void filter_i8_body(
                     __builtin_amdgcn_sched_barrier(0);
                     if (st == 0) SFM_MFMA_I8_C(acc[P + g], a, bq[P + g][st], cinit);
                     else SFM_MFMA_I8(acc[P + g], a, bq[P + g][st]);
-                    if (st == 1 && g == 1) SFM_MFMA_I8_REINIT(cinit, __builtin_bit_cast(u32x4, fr[(S + 1) % D][4]), bi);
-                    epi(g, acc[st], seq_cur, k0[st], k1[st], k2[st], part_cur);
+                    piece_b();
+                    if (st == 1 && g == 1) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        SFM_MFMA_I8_REINIT(cinit, __builtin_bit_cast(u32x4, fr[(S + 1) % D][4]), bi);
+                        __builtin_amdgcn_sched_barrier(0);
+                        piece_b();
+                    }
+                    if (st == 2 && g == 1) sq_n = __builtin_amdgcn_readfirstlane(sq_n + 2);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                load_frag(S, st, t + D, more, true);
+                load_next(S, st, ld_off, off4);
             }
         };
         // whole rounds of D tiles, the remainder after the loop (see the fp16 body: hipcc's waitcnt merge at the back edge).
@@ -2516,21 +2559,28 @@ __device__ __forceinline__ void filter_i8_body(
         constexpr std::integral_constant<int, 0> c0{};
         constexpr std::integral_constant<int, 1> c1{};
         constexpr std::integral_constant<int, 2> c2{};
+        // The train image's partial last tile (nrem != 0, and only the segment that ends the image holds it) is kept out of the
+        // rounds: they stop short of it, their tiles carry neither its test nor the masking code, and it runs through the tested
+        // instantiation below — as the remainder tile, or as slot 1 of a short tail round whose slot-0 tile is the last whole one.
+        const int t_lim = __builtin_amdgcn_readfirstlane(t_end - (nrem != 0 && t_end == tiles ? 1 : 0));
         int t = t_begin;
         for (;;) {
-            const int t_stop = __builtin_amdgcn_readfirstlane(min(sub_t0 + sub_tiles, t_end - (D - 1)));   // (even distance from t)
+            const int t_stop = __builtin_amdgcn_readfirstlane(min(sub_t0 + sub_tiles, t_lim - (D - 1)));   // (even distance from t)
             for (; t < t_stop; t += D) {
-                tile(t, c0, c0);
-                tile(t + 1, c1, c0);
+                tile(t, c0, c0, c0);
+                tile(t + 1, c1, c0, c0);
                 asm volatile("; steady round" ::: "memory");
             }
-            if (t + D > t_end) break;
-            tile(t, c0, c1);                                                 // t - sub_t0 == sub_tiles
-            tile(t + 1, c1, c0);
+            if (t + D > t_lim) break;
+            tile(t, c0, c1, c0);                                             // t - sub_t0 == sub_tiles
+            tile(t + 1, c1, c0, c0);
             asm volatile("; boundary round" ::: "memory");
             t += D;
         }
-        if (t < t_end) tile(t, c0, c2);                                      // (33, 65, 129 tiles: the boundary falls on the remainder tile)
+        if (t < t_end) {                                                     // one or two tiles are left, the first on slot 0
+            tile(t, c0, c2, c2);                                             // (33, 65, 129 tiles: the boundary falls on the remainder tile)
+            if (t + 1 < t_end) tile(t + 1, c1, c0, c2);                      // (the partial tile behind the last whole one)
+        }
         // epilogue of the last tile's groups P .. NG-1 (the MFMAs that completed them were the last instructions issued)
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
         if (t_end > t_begin) {
@@ -2538,7 +2588,7 @@ __device__ __forceinline__ void filter_i8_body(
 #pragma unroll
             for (int g = P; g < NG; ++g)
 #pragma unroll
-                for (int piece = 0; piece < 4; ++piece) epi(piece, acc[g], seq, k0[g], k1[g], k2[g], nrem != 0 && t_end == tiles);
+                for (int piece = 0; piece < 4; ++piece) epi(piece, acc[g], seq, seq | 1, k0[g], k1[g], k2[g], nrem != 0 && t_end == tiles);
         }
         flush(sub, sub_t0, t_end);
         u += t_end - t_begin;
