@@ -42,9 +42,14 @@ __device__ void rodrigues_dev(const double* __restrict__ rv, double* __restrict_
                                  0, r[0], 0, r[0], r[1] + r[1], r[2], 0, r[2], 0,
                                  0, 0, r[0], 0, 0, r[1], r[0], r[1], r[2] + r[2]};
         const double drx[27] = {0, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0};
+        // For the derivative, 1 - cos(theta) as 2 sin^2(theta / 2): the difference rounds to 0 below theta = 1.5e-8 and carries
+        // 1.1e-16 / theta^2 of relative error above, which a2 = c1 / theta (theta / 2 for small angles) hands to dR/dr — 4e-9 at
+        // theta = 1e-8, against the 1e-10 the sums are held to (tests/test_gpu_gn_sweeps.py, edge_problem camera 3).  R itself
+        // keeps cv::Rodrigues' 1 - cos: an absolute 1e-16 there, and the projections and masks keep the oracle's bits.
+        const double sh = sin(0.5 * theta), c1j = 2. * sh * sh;
         for (int i = 0; i < 3; ++i) {
             const double ri = r[i];
-            const double a0 = -s * ri, a1 = (s - 2 * c1 * itheta) * ri, a2 = c1 * itheta;
+            const double a0 = -s * ri, a1 = (s - 2 * c1j * itheta) * ri, a2 = c1j * itheta;
             const double a3 = (c - s * itheta) * ri, a4 = s * itheta;
             for (int k = 0; k < 9; ++k)
                 J[i * 9 + k] = a0 * ((k % 4 == 0) ? 1.0 : 0.0) + a1 * rrt[k] + a2 * drrt[i * 9 + k] + a3 * rx[k] +

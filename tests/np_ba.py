@@ -1,5 +1,8 @@
 """Float64 NumPy reference for the bundle-adjustment linear algebra (csrc/ba_schur.hip): projection, its Jacobians by
-complex-step differentiation, the products with the camera-point coupling W, and the damped Schur step (direct and PCG).
+complex-step differentiation, the products with the camera-point coupling W, and the damped Schur step (direct and PCG);
+and for the Gauss-Newton sweeps and RANSAC scoring (csrc/residual.hip, csrc/ba_dense.hip, project_f64_kernel): the
+normal-equation blocks dense and indexed, both sums of squares, and inlier masks that take the kernels' float32 steps
+exactly and name the entries whose float32 rounding a last-bit difference in double could flip.
 Shares no code with the kernels or the C oracle.
 
 Complex step: for an analytic f, Im f(x + ih) / h = f'(x) + O(h^2) with NO subtraction of nearly equal numbers, so with
@@ -63,9 +66,10 @@ def as_f64(X):
     return np.asarray(X, np.float32)[:, :3].astype(np.float64)
 
 
-def jacobians(cams, K, X, cam_sel=None, pt_sel=None):
+def jacobians(cams, K, X, cam_sel=None, pt_sel=None, which="cp"):
     """Complex-step Jacobians of the projection for the cameras cam_sel x the points pt_sel (default: all):
-    Jc [nc, np, 2, 6] = d(u, v)/d(rvec, tvec),  Jp [nc, np, 2, 3] = d(u, v)/dX."""
+    Jc [nc, np, 2, 6] = d(u, v)/d(rvec, tvec),  Jp [nc, np, 2, 3] = d(u, v)/dX.  which: "c" or "p" evaluates one side only
+    (the other is returned as None)."""
     cams = np.asarray(cams, np.float64).reshape(-1, 6)
     X = as_f64(X)
     if cam_sel is not None:
@@ -73,12 +77,13 @@ def jacobians(cams, K, X, cam_sel=None, pt_sel=None):
     if pt_sel is not None:
         X = X[np.asarray(pt_sel)]
     nc, npts = len(cams), len(X)
-    Jc, Jp = np.empty((nc, npts, 2, 6)), np.empty((nc, npts, 2, 3))
-    for a in range(6):
+    Jc = np.empty((nc, npts, 2, 6)) if "c" in which else None
+    Jp = np.empty((nc, npts, 2, 3)) if "p" in which else None
+    for a in range(6 if Jc is not None else 0):
         c = cams.astype(np.complex128)
         c[:, a] += 1j * H
         Jc[..., a] = project(c, K, X).imag / H
-    for a in range(3):
+    for a in range(3 if Jp is not None else 0):
         x = X.astype(np.complex128)
         x[:, a] += 1j * H
         Jp[..., a] = project(cams, K, x).imag / H
@@ -163,17 +168,181 @@ def indexed_products(cams, K, X, cam_idx, pt_idx, x, v, reverse=False):
     return u, w
 
 
-def normal_blocks(cams, K, X, obs):
-    """B [ncam, 6, 6], C [npt, 3, 3], g_c [ncam, 6], g_p [npt, 3], sumsq and W [ncam, npt, 6, 3] of the dense problem;
-    residual = projection - observation."""
-    Jc, Jp = jacobians(cams, K, X)
-    r = project(np.asarray(cams, np.float64).reshape(-1, 6), K, as_f64(X)) - np.asarray(obs, np.float64)
-    B = np.einsum("ijka,ijkb->iab", Jc, Jc)
-    C = np.einsum("ijka,ijkb->jab", Jp, Jp)
-    gc = np.einsum("ijka,ijk->ia", Jc, r)
-    gp = np.einsum("ijka,ijk->ja", Jp, r)
-    W = np.einsum("ijka,ijkb->ijab", Jc, Jp)
-    return B, C, gc, gp, float((r * r).sum()), W
+def normal_blocks(cams, K, X, obs, want_w=True, pt_block=None, reverse=False, magnitude=False, pt_rows=None):
+    """B [ncam, 6, 6], C [npt, 3, 3], g_c [ncam, 6], g_p [npt, 3], sumsq (the float64 residual's: `res2`) and
+    W [ncam, npt, 6, 3] of the dense problem; residual = projection - observation.
+
+    want_w=False: W is None.  pt_block: work through the points in blocks of that many — nothing of size ncam x npt x 36 is
+    ever held — and add in a DEFINED order: a camera's sums run over the points ascending (reverse=True: descending; within
+    a block along the point axis of the reversed or unreversed view, then block after block), a point's sums over the
+    cameras ascending or descending.  reverse=None: both orders, as a pair of result tuples, the Jacobians evaluated once.
+    magnitude: the sums of |Jc|^T |Jc|, |Jc|^T |r| ... instead, the scale of each row's rounding.  pt_rows (sorted point
+    indices): C and g_p for those points only (the camera sums still run over every point)."""
+    cams = np.asarray(cams, np.float64).reshape(-1, 6)
+    Xd = as_f64(X)
+    ncam, npt = len(cams), len(Xd)
+    obs = np.asarray(obs, np.float64).reshape(ncam, npt, 2)
+    if pt_block is None and reverse is False and not magnitude and pt_rows is None:
+        Jc, Jp = jacobians(cams, K, X)
+        r = project(cams, K, Xd) - obs
+        B = np.einsum("ijka,ijkb->iab", Jc, Jc)
+        C = np.einsum("ijka,ijkb->jab", Jp, Jp)
+        gc = np.einsum("ijka,ijk->ia", Jc, r)
+        gp = np.einsum("ijka,ijk->ja", Jp, r)
+        W = np.einsum("ijka,ijkb->ijab", Jc, Jp) if want_w else None
+        return B, C, gc, gp, float((r * r).sum()), W
+    orders = (False, True) if reverse is None else (bool(reverse),)
+    step = pt_block or max(npt, 1)
+    cam_side = {o: [] for o in orders}
+    pt_side = {o: [] for o in orders}
+    Ws = []
+    for p0 in range(0, npt, step):
+        sel = np.arange(p0, min(npt, p0 + step))
+        Jc, Jp = jacobians(cams, K, X, None, sel, "cp" if pt_rows is None or want_w else "c")
+        r = project(cams, K, Xd[sel]) - obs[:, sel]
+        if want_w:
+            Ws.append(np.einsum("ijka,ijkb->ijab", Jc, Jp))
+        if magnitude:
+            Jc, r = np.abs(Jc), np.abs(r)
+        tB, tg, tr = np.einsum("ijka,ijkb->ijab", Jc, Jc), np.einsum("ijka,ijk->ija", Jc, r), (r * r).sum(-1)
+        for o in orders:
+            cam_side[o].append([np.add.reduce(t[:, ::-1] if o else t, axis=1) for t in (tB, tg, tr)])
+        if pt_rows is None:
+            Jp = np.abs(Jp) if magnitude else Jp
+            tC, tp = np.einsum("ijka,ijkb->ijab", Jp, Jp), np.einsum("ijka,ijk->ija", Jp, r)
+            for o in orders:
+                pt_side[o].append((_ordered_sum(tC, 0, o), _ordered_sum(tp, 0, o)))
+    if pt_rows is not None:
+        rows = np.asarray(pt_rows, np.int64)
+        _, Jp = jacobians(cams, K, X, None, rows, "p")
+        r = project(cams, K, Xd[rows]) - obs[:, rows]
+        if magnitude:
+            Jp, r = np.abs(Jp), np.abs(r)
+        tC, tp = np.einsum("ijka,ijkb->ijab", Jp, Jp), np.einsum("ijka,ijk->ija", Jp, r)
+        for o in orders:
+            pt_side[o].append((_ordered_sum(tC, 0, o), _ordered_sum(tp, 0, o)))
+    W = np.concatenate(Ws, 1) if want_w else None
+    out = []
+    for o in orders:
+        B, gc, res2 = (_ordered_sum(np.stack([blk[k] for blk in cam_side[o]], 0), 0, o) for k in range(3))
+        C, gp = (np.concatenate([blk[k] for blk in pt_side[o]], 0) for k in range(2))
+        out.append((B, C, gc, gp, float(_ordered_sum(res2, 0, o)), W))
+    return tuple(out) if reverse is None else out[0]
+
+
+def indexed_normal_blocks(cams, K, X, obs, cam_idx=None, pt_idx=None, reverse=False, magnitude=False):
+    """B [ncam, 6, 6], C [npt, 3, 3], g_c [ncam, 6], g_p [npt, 3] and res2 summed over the listed observations
+    (cam_idx[o], pt_idx[o]) with obs [nobs, 2]; a repeated observation counts twice.  cam_idx None: camera 0 throughout;
+    pt_idx None: observation o is of point o.  reverse: add the observations in descending order."""
+    cams = np.asarray(cams, np.float64).reshape(-1, 6)
+    obs = np.asarray(obs, np.float64).reshape(-1, 2)
+    ncam, npt, nobs = len(cams), len(X), len(obs)
+    ci = np.zeros(nobs, np.int64) if cam_idx is None else np.asarray(cam_idx, np.int64)
+    pi = np.arange(nobs) if pt_idx is None else np.asarray(pt_idx, np.int64)
+    B, C, gc, gp = np.zeros((ncam, 6, 6)), np.zeros((npt, 3, 3)), np.zeros((ncam, 6)), np.zeros((npt, 3))
+    if nobs == 0:
+        return B, C, gc, gp, 0.0
+    Jc, Jp = pair_jacobians(cams, K, X, ci, pi)
+    r = pair_project(cams, K, X, ci, pi) - obs
+    if magnitude:
+        Jc, Jp, r = np.abs(Jc), np.abs(Jp), np.abs(r)
+    order = np.arange(nobs)[::-1] if reverse else np.arange(nobs)
+    np.add.at(B, ci[order], np.einsum("oka,okb->oab", Jc, Jc)[order])            # ufunc.at adds unbuffered, in the order given
+    np.add.at(gc, ci[order], np.einsum("oka,ok->oa", Jc, r)[order])
+    np.add.at(C, pi[order], np.einsum("oka,okb->oab", Jp, Jp)[order])
+    np.add.at(gp, pi[order], np.einsum("oka,ok->oa", Jp, r)[order])
+    return B, C, gc, gp, float(np.cumsum((r * r).sum(1)[order])[-1])
+
+
+def pair_project(cams, K, X, cam_idx, pt_idx):
+    """Float64 pixels [nobs, 2] of the observations (cam_idx[o], pt_idx[o])."""
+    cams = np.asarray(cams, np.float64).reshape(-1, 6)[np.asarray(cam_idx, np.int64)]
+    return project(cams, K, as_f64(X)[np.asarray(pt_idx, np.int64)][:, None, :])[:, 0]
+
+
+# ---------------------------------------------------------------- the float32 steps of the residual and scoring kernels
+DBL_EPSILON = 2.0 ** -52
+
+
+def project_points(rvec, tvec, K, X):
+    """cv2.projectPoints without distortion on float64 points X [n, 3] (NOT rounded to float32) -> [n, 2] float64, with
+    OpenCV's two conventions: z' = 0 -> z := 1 (project) and cv::Rodrigues' |rvec| < DBL_EPSILON -> R = I exactly."""
+    rvec = np.asarray(rvec, np.float64).reshape(3)
+    if np.sqrt(rvec @ rvec) < DBL_EPSILON:
+        rvec = np.zeros(3)
+    return project(np.hstack([rvec, np.asarray(tvec, np.float64).reshape(3)])[None], K, np.asarray(X, np.float64).reshape(-1, 3))[0]
+
+
+def f32_undecidable(v, rel=1e-12):
+    """True where the float64 value v lies within rel |v| of the midpoint between two neighbouring float32 values: there a
+    last-bit difference of v in double can flip its float32 rounding."""
+    v = np.asarray(v, np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = v.astype(np.float32)
+        lo = np.nextafter(f, np.float32(-np.inf)).astype(np.float64)
+        hi = np.nextafter(f, np.float32(np.inf)).astype(np.float64)
+        f = f.astype(np.float64)
+        d = np.minimum(np.abs(v - 0.5 * (f + lo)), np.abs(v - 0.5 * (f + hi)))
+        return d <= rel * np.abs(v)
+
+
+def sumsq(u, obs, reverse=False):
+    """(float32-rounded metric, float64 res2) of float64 pixels u [..., 2] against float32 observations.  The metric:
+    pu = float32(u), d = float32(pu - obs), squares summed in double — what residual_kernel and the reference's cv2.norm on
+    float32 arrays compute; res2 is the plain sum of (u - obs)^2.  Observations are added ascending (reverse: descending)."""
+    u = np.asarray(u, np.float64).reshape(-1, 2)
+    o32 = np.asarray(obs, np.float32).reshape(-1, 2)
+    d32 = (u.astype(np.float32) - o32).astype(np.float64)                       # float32 - float32: one correctly rounded float32 step
+    d64 = u - o32.astype(np.float64)
+    t32, t64 = (d32 * d32).sum(1), (d64 * d64).sum(1)
+    if reverse:
+        t32, t64 = t32[::-1], t64[::-1]
+    return (float(np.cumsum(t32)[-1]), float(np.cumsum(t64)[-1])) if len(u) else (0.0, 0.0)
+
+
+def sumsq_flip_allowance(u, obs):
+    """The most the float32 metric can move if every undecidable coordinate of u rounds the other way: pu moves by one
+    float32 spacing s, d = pu - obs by s (+ its own rounding, s / 2 at the most), d^2 by at most 2 |d| (1.5 s) + (1.5 s)^2."""
+    u = np.asarray(u, np.float64).reshape(-1, 2)
+    und = f32_undecidable(u)
+    if not und.any():
+        return 0.0
+    uu = u[und]
+    f = uu.astype(np.float32)
+    s = 1.5 * np.maximum(np.nextafter(f, np.float32(np.inf)).astype(np.float64) - f, f - np.nextafter(f, np.float32(-np.inf)).astype(np.float64))
+    d = np.abs(uu - np.asarray(obs, np.float32).reshape(-1, 2).astype(np.float64)[und])
+    return float((2 * d * s + s * s).sum())
+
+
+def pnp_inliers(u, obs, thr2):
+    """The kernels' inlier test on float64 pixels u [..., n, 2]: ex = float32(obs - float32(u)), err = float32(double(ex)^2 +
+    double(ey)^2), err <= thr2 (inclusive).  Returns (mask, undecidable) — undecidable where u or v could round either way."""
+    u = np.asarray(u, np.float64)
+    e = (np.asarray(obs, np.float32).reshape(-1, 2) - u.astype(np.float32)).astype(np.float64)
+    err = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]).astype(np.float32)
+    return err <= np.float32(thr2), f32_undecidable(u).any(-1)
+
+
+def score_pnp(poses, K, X, obs, thr2):
+    """(counts [h], mask [h, n] bool, undecidable [h, n] bool) of sfm_score_pnp."""
+    mask, und = pnp_inliers(project(np.asarray(poses, np.float64).reshape(-1, 6), K, as_f64(X)), obs, thr2)
+    return mask.sum(1), mask, und
+
+
+def score_essential(Es, x1n, x2n, thr2):
+    """(counts [h], mask [h, n] bool, undecidable [h, n] bool) of sfm_score_essential: the Sampson distance
+    (x2^T E x1)^2 / ((E x1)_0^2 + (E x1)_1^2 + (E^T x2)_0^2 + (E^T x2)_1^2) in double, ONE cast of the quotient to float32,
+    err <= thr2 (inclusive).  Undecidable: the quotient could round either way."""
+    E = np.asarray(Es, np.float64).reshape(-1, 3, 3)
+    h1 = np.c_[np.asarray(x1n, np.float64).reshape(-1, 2), np.ones(len(x1n))]
+    h2 = np.c_[np.asarray(x2n, np.float64).reshape(-1, 2), np.ones(len(x2n))]
+    Ex1 = np.einsum("hab,nb->hna", E, h1)
+    Etx2 = np.einsum("hba,nb->hna", E, h2)
+    num = np.einsum("na,hna->hn", h2, Ex1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = num * num / (Ex1[..., 0] ** 2 + Ex1[..., 1] ** 2 + Etx2[..., 0] ** 2 + Etx2[..., 1] ** 2)
+        mask = q.astype(np.float32) <= np.float32(thr2)
+    return mask.sum(1), mask, f32_undecidable(q)
 
 
 def _damp(M, lam):

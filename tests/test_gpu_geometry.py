@@ -1,7 +1,9 @@
 """HIP path vs oracle for triangulation (sfm.py:53-54), reprojection error (sfm.py:79-100), the
 Gauss-Newton sweep (sfm.py:104-157) and RANSAC scoring (sfm.py:67,307), through the C-ABI.
 Tolerances: north_star asks 1e-4 relative; these kernels mirror the oracle's operation order so the
-tests hold them to 1e-6 (float32 outputs) / 1e-9 (fp64 sums); integer masks bit-exact."""
+tests hold them to 1e-6 (float32 outputs) / 1e-9 (fp64 sums); integer masks bit-exact.
+test_gpu_gn_sweeps.py holds the sweeps, the scoring kernels and project_points_f64 to the float64 reference of np_ba.py on
+every launch path (both fold levels, PP = 2 and 4, every index combination), at the camera-table edges and on exact ties."""
 import numpy as np
 import pytest
 import torch
