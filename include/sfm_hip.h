@@ -1004,6 +1004,91 @@ int sfm_track_triangulate(const int32_t* counts_dev, const int32_t* track_off_de
                           int n_img, const float* kp_dev, const double* P_dev, int64_t n_nodes, float* X_dev, float* err_dev,
                           float* depth_dev, int32_t* flags_dev, float* max_err_dev, void* stream);
 
+/* ------------------------------------------------------------------------
+ * TRACKS-REFINE (no reference counterpart; csrc/tracks_refine.hip, docs/tracks.md §8): robust refinement of the N-view points and
+ * pruning of single observations.  counts_dev, track_off_dev, obs_node_dev, img_off_dev, kp_dev, P_dev and n_nodes are
+ * sfm_track_triangulate's and are read and clamped as it clamps them (T to 0..N/2+1, nobs to 0..N, 0 <= lo <= hi <= nobs).  Every
+ * float64 operation is correctly rounded in the order written here (no FMA, no reassociation, IEEE / and sqrt); every integer output
+ * is a count, a rank or a copy: no word depends on the order in which atomics land (there are none).  tests/np_tracks_refine.py
+ * restates every output word from this text.  The ranges [lo, hi) of the tracks must not OVERLAP (sfm_track_build's and
+ * sfm_track_prune's never do): where they do, as with a count above the true one over offsets nobody wrote, the outputs of both
+ * calls are unspecified, but every read and write stays inside the arrays: the state a lane keeps in a row of depth_dev is checked
+ * against n_img and N each time it is read, and sfm_track_prune writes no observation at or past row N.
+ *
+ * sfm_track_refine — one lane per track t < counts[0].  X_in_dev float32 [N / 2 + 1][3] and flags_in_dev int32 [N / 2 + 1] are
+ *   sfm_track_triangulate's outputs (not aliased by the outputs here).  huber > 0 px or +inf (plain least squares); obs_thresh > 0
+ *   px; iters, iters2 in 0..50.  ws_dev holds the camera centres, filled by a kernel of the same call: with p = an image's P,
+ *     a00 = p5 * p10 - p6 * p9;   a01 = p2 * p9 - p1 * p10;   a02 = p1 * p6 - p2 * p5
+ *     a10 = p6 * p8 - p4 * p10;   a11 = p0 * p10 - p2 * p8;   a12 = p2 * p4 - p0 * p6
+ *     a20 = p4 * p9 - p5 * p8;    a21 = p1 * p8 - p0 * p9;    a22 = p0 * p5 - p1 * p4
+ *     det = (p0 * a00 + p1 * a10) + p2 * a20;    C[r] = -(((a_r0 * p3 + a_r1 * p7) + a_r2 * p11) / det)        (r = 0..2)
+ *   At a point q = (q0, q1, q2), for an observation with keypoint (kx, ky) promoted to float64 and P its image's matrix:
+ *     h_r = ((P[4r] * q0 + P[4r + 1] * q1) + P[4r + 2] * q2) + P[4r + 3];   u = h_0 / h_2;  v = h_1 / h_2
+ *     du = u - kx;  dv = v - ky;  e = sqrt(du * du + dv * dv)
+ *   start      x = X_in[t] promoted to float64.  If bit 1 of flags_in[t] is clear or a coordinate of x is not finite the track is
+ *              NOT STARTED: X_out[t] = X_in[t], no observation is an inlier, flags = n_inl = steps = 0, max_err = 0, cos_min = 1,
+ *              err and depth as below at X_in[t].
+ *   usable     an observation whose node lies in 0..N-1 and for which, at the start point, h_2 is finite and > 0 and e is finite.
+ *              The set is fixed; an observation outside it takes no part in anything and is no inlier.
+ *   an attempt (the loop of both phases; `active` = the usable observations in phase 1, the inliers in phase 2; lam = 1e-3 at the
+ *              start of a phase; cost = the sum of rho(e) over the active observations at x, in observation order from 0):
+ *                w = 1 when e <= huber, else huber / e                                 (phase 2: w = 1)
+ *                ja[k] = (P[k] - u * P[8 + k]) / h_2;  jb[k] = (P[4 + k] - v * P[8 + k]) / h_2              (k = 0..2)
+ *                A[a][b] = (A[a][b] + w * (ja[a] * ja[b])) + w * (jb[a] * jb[b])       (a <= b)
+ *                g[a]    = (g[a] + w * (ja[a] * du)) + w * (jb[a] * dv)                (over the active observations in order, from 0)
+ *                s00 = A00 + lam * A00;  s11 = A11 + lam * A11;  s22 = A22 + lam * A22
+ *                c00 = s11 * s22 - A12 * A12;  c01 = A02 * A12 - A01 * s22;  c02 = A01 * A12 - A02 * s11
+ *                c11 = s00 * s22 - A02 * A02;  c12 = A01 * A02 - s00 * A12;  c22 = s00 * s11 - A01 * A01
+ *                det = (s00 * c00 + A01 * c01) + A02 * c02
+ *                d0 = -(((c00 * g0 + c01 * g1) + c02 * g2) / det);  d1 = -(((c01 * g0 + c11 * g1) + c12 * g2) / det)
+ *                d2 = -(((c02 * g0 + c12 * g1) + c22 * g2) / det);  trial point x + d
+ *              ACCEPTED iff det != 0, d is finite, every active observation has a finite h_2 > 0 at the trial point, and the
+ *              trial cost (same sum, at the trial point) is < cost.  Accepted: x = x + d, cost = trial cost, lam = lam / 10,
+ *              steps + 1; rejected: lam = lam * 10.  There is no stopping rule: a phase makes all its attempts.
+ *   phase 1    iters attempts with rho(e) = e * e / 2 when e <= huber, else huber * (e - huber / 2).
+ *   inliers    the usable observations with e <= obs_thresh at the end of phase 1; n_inl of them.  The set is fixed from here on.
+ *   phase 2    only when n_inl >= 2: iters2 attempts with rho(e) = e * e / 2.
+ *   X_out_dev  float32 [N / 2 + 1][3] = (float)x.  The outputs below are taken at Xf = X_out[t] promoted to float64:
+ *   err_dev, depth_dev  float32 [N]: err = (float)e, depth = (float)h_2 at Xf for a node in 0..N-1, both NaN otherwise (the
+ *              formulas of sfm_track_triangulate).  Between its passes the call keeps one int32 per observation in the rows of
+ *              depth_dev that it overwrites at the end.
+ *   inlier_dev uint8 [N]: 1 for an inlier, else 0.     n_inl_dev int32 [N / 2 + 1].     steps_dev int32 [N / 2 + 1]: accepted
+ *              attempts of both phases.
+ *   max_err_dev float32 [N / 2 + 1]: from m = 0 over the INLIERS in observation order, m = err when err > m or err is NaN.
+ *   cos_min_dev float32 [N / 2 + 1]: rays r_i = Xf - C[image] (component by component) of the first 64 inliers in observation
+ *              order; n_i = (r_i0 * r_i0 + r_i1 * r_i1) + r_i2 * r_i2; from m = 1, over the pairs i < j (i outer, j inner)
+ *              c = ((r_i0 * r_j0 + r_i1 * r_j1) + r_i2 * r_j2) / sqrt(n_i * n_j), m = c when c < m (a NaN never is);
+ *              cos_min = (float)m: 1 with fewer than two inliers.  There is no acos on the device: callers compare cosines.
+ *   flags_dev  int32 [N / 2 + 1]: bit 0 = n_inl >= 2; bit 1 = X_out[t] is finite (0 for a track that is not started).
+ *   Every float32 NaN that is written is the quiet NaN 0x7FC00000.  Rows at or past counts[0] / counts[1] are not written.
+ *
+ * sfm_track_prune — keeps track t iff flags[t] == 3 and n_inl[t] >= min_len (>= 2) and (double)max_err[t] <= max_reproj (+inf
+ *   switches it off; a NaN max_err fails) and (double)cos_min[t] <= max_cos (1 switches it off).  X_dev, inlier_dev, n_inl_dev,
+ *   max_err_dev, cos_min_dev, flags_dev: sfm_track_refine's outputs.  Kept tracks in ascending old order are tracks 0..T'-1 and hold
+ *   their observations with inlier != 0 in the old order; ranks come from per-block counts and a one-workgroup scan, no host wait.
+ *   track_off2_dev int32 [N / 2 + 2] (T' + 1 words written), obs_node2_dev int32 [N] (nobs'), X2_dev float32 [N / 2 + 1][3] (the
+ *   words of X), track_src_dev int32 [N / 2 + 1] (the old index): T' rows each.  counts2_dev int32[4] = (T', nobs', tracks dropped,
+ *   observations dropped from kept tracks).  Nothing at or past the counted rows is written.  (counts2, track_off2, obs_node2) have
+ *   the shape sfm_track_build leaves: sfm_track_triangulate and sfm_track_refine run on them again.
+ *
+ * Errors (SFM_ERR_ARG, before any device call): n_nodes outside 0..2^31-1, n_img outside 1..65 536, huber or obs_thresh NaN or <= 0,
+ *   iters or iters2 outside 0..50, min_len outside 2..2^31-1, a NaN max_reproj or max_cos, NULL where the count is non-zero (the
+ *   per-track arrays, counts, P, img_off and the workspaces always), a workspace smaller than the _ws_bytes twin says.  The _ws_bytes
+ *   twins return 0 for invalid sizes.
+ * ---------------------------------------------------------------------- */
+size_t sfm_track_refine_ws_bytes(int n_img);
+int sfm_track_refine(const int32_t* counts_dev, const int32_t* track_off_dev, const int32_t* obs_node_dev, const int32_t* img_off_dev,
+                     int n_img, const float* kp_dev, const double* P_dev, int64_t n_nodes, const float* X_in_dev, const int32_t* flags_in_dev,
+                     double huber, double obs_thresh, int iters, int iters2, float* X_out_dev, uint8_t* inlier_dev, float* err_dev,
+                     float* depth_dev, int32_t* n_inl_dev, float* max_err_dev, float* cos_min_dev, int32_t* steps_dev, int32_t* flags_dev,
+                     void* ws_dev, size_t ws_bytes, void* stream);
+size_t sfm_track_prune_ws_bytes(int64_t n_nodes);
+int sfm_track_prune(const int32_t* counts_dev, const int32_t* track_off_dev, const int32_t* obs_node_dev, int64_t n_nodes, const float* X_dev,
+                    const uint8_t* inlier_dev, const int32_t* n_inl_dev, const float* max_err_dev, const float* cos_min_dev,
+                    const int32_t* flags_dev, int64_t min_len, double max_reproj, double max_cos, int32_t* track_off2_dev,
+                    int32_t* obs_node2_dev, float* X2_dev, int32_t* track_src_dev, int32_t* counts2_dev, void* ws_dev, size_t ws_bytes,
+                    void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

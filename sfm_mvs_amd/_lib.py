@@ -118,6 +118,11 @@ SIGNATURES = {
     "sfm_track_build_ws_bytes": (_sz, [_i64]),
     "sfm_track_build": (_int, [_vp, _vp, _i64, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sfm_track_triangulate": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_track_refine_ws_bytes": (_sz, [_int]),
+    "sfm_track_refine": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _sz, _vp]),
+    "sfm_track_prune_ws_bytes": (_sz, [_i64]),
+    "sfm_track_prune": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

@@ -4,7 +4,9 @@ A node is `img_off[image] + keypoint`.  `match_edges` turns the device-resident 
 graph edges, `track_components` labels the connected components, `build_tracks` keeps the components that name no image twice and
 orders them, `triangulate_tracks` triangulates each from all its views.  All four take and return device tensors and never wait
 for the host; `run_tracks` composes them, reads the counts once and downloads once, and returns the points and observations in the
-form `ba.bundle_adjust_schur(cams, K, X, obs, cam_idx, pt_idx)` takes."""
+form `ba.bundle_adjust_schur(cams, K, X, obs, cam_idx, pt_idx)` takes.  `refine_tracks` and `prune_tracks` ("TRACKS-REFINE";
+docs/tracks.md §8) refine each point under a Huber loss, flag observations one by one and keep a track with its inliers only:
+`run_tracks(robust=True)`."""
 import numpy as np
 import torch
 
@@ -143,6 +145,98 @@ def triangulate_tracks(counts, track_off, obs_node, img_off, keypoints, P, out=N
     return X, err, depth, flags, max_err
 
 
+def _track_inputs(who, counts, track_off, obs_node, img_off, keypoints, P):
+    n_img = _offsets(img_off)
+    require_cuda(keypoints, P)
+    _i32(counts, "counts")
+    _i32(track_off, "track_off")
+    _i32(obs_node, "obs_node")
+    n = int(obs_node.numel())
+    if keypoints.dtype != torch.float32 or tuple(keypoints.shape) != (n, 2) or not keypoints.is_contiguous():
+        raise SfmHipError(f"{who}: keypoints must be a contiguous float32 [N, 2] device tensor")
+    if P.dtype != torch.float64 or P.numel() != 12 * n_img or not P.is_contiguous():
+        raise SfmHipError(f"{who}: P must be a contiguous float64 [n_img, 12] device tensor")
+    if counts.numel() < 2 or track_off.numel() < n // 2 + 2:
+        raise SfmHipError(f"{who}: counts must hold (tracks, observations) and track_off N // 2 + 2 words")
+    return n_img, n
+
+
+def _typed(t, dtype, shape, what):
+    require_cuda(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise SfmHipError(f"tracks: {what} must be a contiguous {dtype} device tensor of shape {tuple(shape)}")
+    return t
+
+
+def refine_tracks(counts, track_off, obs_node, img_off, keypoints, P, X, flags, huber=1.0, obs_thresh=2.0, iters=10, iters2=5, out=None):
+    """sfm_track_refine: one lane per track, the counts read on the device.  X [N // 2 + 1, 3] f32 and flags [N // 2 + 1] i32 are
+    `triangulate_tracks`' outputs; huber (px, > 0, inf = plain least squares) is the Huber width of phase 1, obs_thresh (px) the
+    inlier bound, iters / iters2 (0..50) the Levenberg-Marquardt attempts of the two phases.  Returns (X_out [N // 2 + 1, 3] f32,
+    inlier [N] u8, err [N] f32, depth [N] f32, n_inl [N // 2 + 1] i32, max_err f32, cos_min f32, steps i32, flags i32), of which the
+    first counts[0] / counts[1] rows are written.  No host wait."""
+    from .ops import _workspace
+    n_img, n = _track_inputs("refine_tracks", counts, track_off, obs_node, img_off, keypoints, P)
+    dev, cap = obs_node.device, n // 2 + 1
+    _typed(X, torch.float32, (cap, 3), "X")
+    _typed(flags, torch.int32, (cap,), "flags")
+    if out is None:
+        f32, i32 = torch.float32, torch.int32
+        out = (torch.empty((cap, 3), dtype=f32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=f32, device=dev),
+               torch.empty(n, dtype=f32, device=dev), torch.empty(cap, dtype=i32, device=dev), torch.empty(cap, dtype=f32, device=dev),
+               torch.empty(cap, dtype=f32, device=dev), torch.empty(cap, dtype=i32, device=dev), torch.empty(cap, dtype=i32, device=dev))
+    X_out, inlier, err, depth, n_inl, max_err, cos_min, steps, flags_out = out
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_track_refine_ws_bytes(n_img))
+    with on_device(dev):
+        check(L.sfm_track_refine(ptr(counts), ptr(track_off), ptr(obs_node) if n else None, ptr(img_off), n_img, ptr(keypoints) if n else None,
+                                 ptr(P), n, ptr(X), ptr(flags), float(huber), float(obs_thresh), int(iters), int(iters2), ptr(X_out),
+                                 ptr(inlier) if n else None, ptr(err) if n else None, ptr(depth) if n else None, ptr(n_inl), ptr(max_err),
+                                 ptr(cos_min), ptr(steps), ptr(flags_out), ptr(ws), ws.numel(), stream_ptr()), "sfm_track_refine")
+    return X_out, inlier, err, depth, n_inl, max_err, cos_min, steps, flags_out
+
+
+def max_cos_of(min_angle_deg):
+    """The cosine `sfm_track_prune` compares with: a track passes when two of its inlier rays open at least `min_angle_deg` degrees
+    (None or 0: every track passes)."""
+    return 1.0 if min_angle_deg is None or min_angle_deg <= 0 else float(np.cos(np.deg2rad(float(min_angle_deg))))
+
+
+def prune_tracks(counts, track_off, obs_node, X, inlier, n_inl, max_err, cos_min, flags, min_len=2, max_reproj=None, min_angle_deg=None,
+                 max_cos=None, out=None):
+    """sfm_track_prune on `refine_tracks`' outputs: keeps the tracks with flags == 3, n_inl >= min_len, max_err <= max_reproj (None:
+    no bound) and two inlier rays at least min_angle_deg apart (None: no bound; max_cos overrides the cosine the angle turns into),
+    and of those the inlier observations.  Returns (track_off2 [N // 2 + 2] i32, obs_node2 [N] i32, X2 [N // 2 + 1, 3] f32,
+    track_src [N // 2 + 1] i32, counts2 [4] i32 = (tracks, observations, tracks dropped, observations dropped from kept tracks)); the
+    first three with counts2 have the shape `build_tracks` leaves.  No host wait."""
+    from .ops import _workspace
+    _i32(counts, "counts")
+    _i32(track_off, "track_off")
+    _i32(obs_node, "obs_node")
+    n, dev = int(obs_node.numel()), obs_node.device
+    cap = n // 2 + 1
+    if counts.numel() < 2 or track_off.numel() < n // 2 + 2:
+        raise SfmHipError("prune_tracks: counts must hold (tracks, observations) and track_off N // 2 + 2 words")
+    _typed(X, torch.float32, (cap, 3), "X")
+    _typed(inlier, torch.uint8, (n,), "inlier")
+    _typed(n_inl, torch.int32, (cap,), "n_inl")
+    _typed(max_err, torch.float32, (cap,), "max_err")
+    _typed(cos_min, torch.float32, (cap,), "cos_min")
+    _typed(flags, torch.int32, (cap,), "flags")
+    if out is None:
+        out = (torch.empty(n // 2 + 2, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty((cap, 3), dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+               torch.empty(4, dtype=torch.int32, device=dev))
+    track_off2, obs_node2, X2, track_src, counts2 = out
+    L = _lib.lib()
+    ws = _workspace(dev, L.sfm_track_prune_ws_bytes(n))
+    with on_device(dev):
+        check(L.sfm_track_prune(ptr(counts), ptr(track_off), ptr(obs_node) if n else None, n, ptr(X), ptr(inlier) if n else None, ptr(n_inl),
+                                ptr(max_err), ptr(cos_min), ptr(flags), int(min_len), float("inf") if max_reproj is None else float(max_reproj),
+                                max_cos_of(min_angle_deg) if max_cos is None else float(max_cos), ptr(track_off2), ptr(obs_node2) if n else None,
+                                ptr(X2), ptr(track_src), ptr(counts2), ptr(ws), ws.numel(), stream_ptr()), "sfm_track_prune")
+    return track_off2, obs_node2, X2, track_src, counts2
+
+
 def _scene_tensors(n_query, pairs, keypoints, P, dev):
     sizes = [int(k.shape[0]) for k in keypoints]
     img_off = image_offsets(sizes, dev)
@@ -153,28 +247,41 @@ def _scene_tensors(n_query, pairs, keypoints, P, dev):
     return img_off, kp, nq, pr, Pd, int(sum(sizes))
 
 
-def run_tracks(store, n_query, pairs, keypoints, P, ratio=0.70, keep=None, min_len=2, max_len=None, max_reproj=None, rounds=TRACK_ROUNDS):
+def run_tracks(store, n_query, pairs, keypoints, P, ratio=0.70, keep=None, min_len=2, max_len=None, max_reproj=None, rounds=TRACK_ROUNDS,
+               robust=False, huber=1.0, obs_thresh=2.0, min_angle_deg=None, refine_iters=10):
     """Match store -> tracks -> N-view points.  store, n_query, pairs as `sharded.match_pairs_sharded` returns and takes them;
     keypoints: list over images of [n_i, 2] float32 device tensors; P: [n_img, 3, 4] float64 (host).  Keeps the tracks whose
     triangulation has flags == 3 (every depth positive, a finite point) and, if max_reproj is given, a largest reprojection error
     <= max_reproj.  Returns host arrays: points (T', 3) f32, obs (nobs', 2) f32, cam_idx, pt_idx (nobs',) i32, track_len (T',) i32,
     counts (6,) as sfm_track_build writes them, status (2,) of the labelling.  Two host waits: the counts (with the status) and one
-    download; each batch of `rounds` rounds the labelling still needs after the first costs one more read of the status."""
+    download; each batch of `rounds` rounds the labelling still needs after the first costs one more read of the status.
+    robust=True: every point is refined by `refine_tracks(huber, obs_thresh, iters=refine_iters)` and `prune_tracks(min_len, max_reproj,
+    min_angle_deg)` keeps a track with its inlier observations only instead of dropping it whole; the same keys come back from the
+    pruned set, with `obs_dropped` and `tracks_dropped`; still two host waits (the first also reads the pruned counts)."""
     dev = store.device
     store = store.contiguous()
     img_off, kp, nq, pr, Pd, n = _scene_tensors(n_query, pairs, keypoints, P, dev)
     edges = match_edges(store, nq, pr, img_off, ratio, keep)
-    head = torch.empty(8, dtype=torch.int32, device=dev)
-    counts, status = head[:6], head[6:]
+    head = torch.empty(12 if robust else 8, dtype=torch.int32, device=dev)
+    counts, status = head[:6], head[6:8]
     labels, lowered = None, 0
     while True:
         labels, _ = track_components(edges, n, rounds, labels, status)
         node_track, track_off, obs_node, _ = build_tracks(labels, img_off, min_len, max_len, counts)
         X, err, depth, flags, max_err = triangulate_tracks(counts, track_off, obs_node, img_off, kp, Pd)
-        host_head = head.cpu().numpy()                                # host wait 1: the counts and the status
+        if robust:
+            refined = refine_tracks(counts, track_off, obs_node, img_off, kp, Pd, X, flags, huber, obs_thresh, refine_iters)
+            pruned = prune_tracks(counts, track_off, obs_node, refined[0], refined[1], refined[4], refined[5], refined[6], refined[8], min_len,
+                                  max_reproj, min_angle_deg, out=(torch.empty(n // 2 + 2, dtype=torch.int32, device=dev),
+                                                                  torch.empty(n, dtype=torch.int32, device=dev),
+                                                                  torch.empty((n // 2 + 1, 3), dtype=torch.float32, device=dev),
+                                                                  torch.empty(n // 2 + 1, dtype=torch.int32, device=dev), head[8:]))
+        host_head = head.cpu().numpy()                                # host wait 1: the counts and the status (and the pruned counts)
         lowered += int(host_head[7])
         if host_head[6]:
             break
+    if robust:
+        return _robust_result(host_head, lowered, pruned, img_off, kp)
     T, nobs = int(host_head[0]), int(host_head[1])
     nodes = obs_node[:nobs].long()
     cam = (torch.searchsorted(img_off[:-1].contiguous(), obs_node[:nobs], right=True) - 1).to(torch.int32)
@@ -197,6 +304,22 @@ def run_tracks(store, n_query, pairs, keypoints, P, ratio=0.70, keep=None, min_l
     return dict(points=np.ascontiguousarray(Xh[good]), obs=np.ascontiguousarray(obs[sel]), cam_idx=np.ascontiguousarray(camh[sel]),
                 pt_idx=new_id[track[sel]].astype(np.int32), track_len=length[good].astype(np.int32), counts=host_head[:6].copy(),
                 status=np.array([int(host_head[6]), lowered], np.int32))
+
+
+def _robust_result(host_head, lowered, pruned, img_off, kp):
+    """The one download of run_tracks(robust=True): every pruned track is returned, with its inlier observations."""
+    track_off2, obs_node2, X2, _, _ = pruned
+    T, nobs = int(host_head[8]), int(host_head[9])
+    nodes = obs_node2[:nobs].long()
+    cam = (torch.searchsorted(img_off[:-1].contiguous(), obs_node2[:nobs], right=True) - 1).to(torch.int32)
+    words = torch.cat([X2[:T].reshape(-1).view(torch.int32), track_off2[:T + 1], cam, kp.index_select(0, nodes).reshape(-1).view(torch.int32)])
+    host = words.cpu().numpy()                                        # host wait 2: the one download
+    pos = np.cumsum([0, 3 * T, T + 1, nobs])
+    length = np.diff(host[pos[1]:pos[2]].astype(np.int64))
+    return dict(points=np.ascontiguousarray(host[pos[0]:pos[1]].view(np.float32).reshape(T, 3)),
+                obs=np.ascontiguousarray(host[pos[3]:].view(np.float32).reshape(nobs, 2)), cam_idx=np.ascontiguousarray(host[pos[2]:pos[3]]),
+                pt_idx=np.repeat(np.arange(T), length).astype(np.int32), track_len=length.astype(np.int32), counts=host_head[:6].copy(),
+                status=np.array([int(host_head[6]), lowered], np.int32), tracks_dropped=int(host_head[10]), obs_dropped=int(host_head[11]))
 
 
 def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70):
