@@ -1089,6 +1089,90 @@ int sfm_track_prune(const int32_t* counts_dev, const int32_t* track_off_dev, con
                     int32_t* obs_node2_dev, float* X2_dev, int32_t* track_src_dev, int32_t* counts2_dev, void* ws_dev, size_t ws_bytes,
                     void* stream);
 
+/* ------------------------------------------------------------------------
+ * TRACKS-BA (no reference counterpart; csrc/tracks_ba.hip, docs/tracks.md §9): bundle adjustment of the tracks, a fixed-order sparse
+ * Schur Levenberg-Marquardt with a Huber loss.  It stands beside sfm_project_residual / sfm_ba_schur_indexed (fp64 atomics, float32
+ * points, no loss) and changes nothing of theirs.
+ *
+ * Problem layout (every entry point): cams_dev float64 [ncam][6] (rvec, tvec), K_host float64 [9], X_dev FLOAT64 [npt][3], obs_dev
+ *   float32 [nobs][2];  1 <= ncam < 2^24, 1 <= npt <= 2^31-1, 0 <= nobs <= 2^31-1.
+ *   point side   track_off_dev int32 [npt + 1], cam_idx_dev, pt_idx_dev int32 [nobs]: point-major as tracks.run_tracks returns them,
+ *                observation o belongs to track pt_idx[o] and track_off is its CSR.
+ *   camera side  cam_off_dev int32 [ncam + 1], cam_obs_dev int32 [nobs]: the stable counting sort of the observations by camera,
+ *                observation indices ascending inside a camera.
+ *   No index is trusted.  An observation whose cam_idx is outside 0..ncam-1 or whose pt_idx is outside 0..npt-1 is inactive; a CSR
+ *   row is clamped to 0 <= lo <= hi <= nobs; an entry of cam_obs outside 0..nobs-1, or naming an observation whose cam_idx is not the
+ *   row's camera, adds nothing.  The camera rows are cut into chunks of 256 entries, granted in camera order while fewer than
+ *   nobs / 256 + ncam are in use (rows that overlap can ask for more; consistent rows never do): a camera reads the entries of the
+ *   chunks it was granted.  Every read and write stays inside the arrays, whatever the CSRs hold.
+ *
+ * The workspace belongs to ONE linearisation: sfm_track_ba_sweep leaves the rows in it, sfm_track_ba_product and sfm_track_ba_step
+ *   read them.  A trial sweep therefore takes a second workspace (track_ba.py keeps two and swaps them on acceptance).  The rows
+ *   start at the first 256-byte aligned address of ws_dev: float64 [nobs][20].
+ *
+ * sfm_track_ba_sweep — linearisation at (cams, X).
+ *   projection  as sfm_project_residual: X' = R(rvec) X + t, u = fx X'/Z' + cx, v = fy Y'/Z' + cy, r = (u, v) - obs in float64.
+ *   active set  mode 0: observation o is active iff its indices are in range, Z' is finite and > 0 and r is finite; active_dev uint8
+ *               [nobs] is WRITTEN.  mode 1 (a trial point): active_dev is READ and stays; an active observation (indices in range)
+ *               whose Z' is not finite and > 0 or whose r is not finite counts in `crossed` and contributes nothing.  The caller
+ *               refuses a trial with crossed > 0 (the rule of sfm_track_refine: no step may put a point behind a camera that sees it).
+ *   loss        e = |r|;  w = 1 when e <= huber, else huber / e;  rho = e * e when e <= huber, else 2 * huber * e - huber * huber
+ *               (continuous at e = huber; huber = +inf: plain least squares).
+ *   rows        per observation 20 doubles: sqrt(w) Jc (d(u,v)/d(rvec,tvec), 2 x 6: the u row, then the v row), sqrt(w) Jp (d(u,v)/dX,
+ *               2 x 3), sqrt(w) r (2).  Rows of observations that do not contribute are all zero.
+ *   blocks      JtJ_pt_dev [npt][9] = C_j = sum Jp^T w Jp, Jtr_pt_dev [npt][3] = sum Jp^T w r, JtJ_cam_dev [ncam][36] = B_i = sum
+ *               Jc^T w Jc, Jtr_cam_dev [ncam][6] = sum Jc^T w r (symmetric blocks written in full).  A point or camera without
+ *               contributing observations gets zeros.
+ *   stat_dev    float64 [2] = (sum of rho, sum of e * e) over the contributing observations.
+ *   count_dev   int32 [3] = (contributing observations, crossed, contributing observations with e > huber).
+ *
+ * Summation order — the contract.  Every sum is a fixed function of the CSRs and of the data; none depends on the grid, on the waves
+ *   in flight or on the order in which workgroups finish.  THERE ARE NO FLOATING-POINT ATOMICS in csrc/tracks_ba.hip.
+ *   point side   G = 8 lanes per track (SFM_TBA_GROUP): lane l adds observations lo + l, lo + l + G, ... in ascending order, the G
+ *                partial sums meet in a xor tree (strides G / 2 .. 1).
+ *   camera side  a camera's list is cut into chunks of 256 observations; one workgroup sums a chunk (a lane per observation, a xor
+ *                tree over each wave of 64, strides 32 .. 1, then the four waves in ascending order); a fold kernel adds the chunk
+ *                sums of a camera in ascending order.
+ *   cost, counts the same workgroup tree over 256 consecutive observations, then one workgroup of 1024 lanes: lane l adds the block
+ *                sums l, l + 1024, ... ascending, then a tree (strides 512 .. 1).
+ *   Appending tracks and cameras after a problem (not observing its points) leaves the blocks of its rows bit for bit.  The values
+ *   are held to 1e-10 of the largest entry against tests/np_track_ba.py, not to the bit (a * b + c may be fused).
+ *
+ * sfm_track_ba_product — over the rows a sweep left in ws_dev (the weights are in them):
+ *   mode 0: out [npt][3] = W^T in, u_j = sum_o Jp_o^T (Jc_o in[cam_idx[o]]);  mode 1: out [ncam][6] = W in, w_i = sum_o Jc_o^T (Jp_o
+ *   in[pt_idx[o]]).  The summation orders of the sweep's point and camera side.
+ *
+ * sfm_track_ba_step — one damped step, the sparse twin of sfm_ba_schur_solve: Bd = B with its diagonal times (1 + lam), Cd likewise;
+ *   S dc = g_c - W Cd^-1 g_p with S = Bd - W Cd^-1 W^T by block-Jacobi (Bd^-1) preconditioned conjugate gradients over the two
+ *   products; dp = Cd^-1 (g_p - W^T dc).  The update is parameters - step.  fix_first_camera: camera 0 does not move.  Every vector
+ *   operation of the camera side runs in one workgroup with fixed-order sums, the scalars stay on the device.
+ *   host waits   one per look at r.r, taken before iterations 0, 5, 10, ... while iterations remain (stop: r.r <= cg_tol^2 rhs.rhs):
+ *                it / 5 + 1 when the bound stops it after `it` iterations, (cg_iters + 4) / 5 when cg_iters runs out, 1 for
+ *                cg_iters = 0.  The status comes with the first look.  dc_dev [ncam][6] and dp_dev [npt][3] are complete in stream
+ *                order, not at return.  track_ba.bundle_adjust_tracks adds ONE wait per attempt, its read of stat and count.
+ *   status_host  bit 0: a singular camera block (a zero or non-finite pivot; its preconditioner block is the identity); bit 1: a
+ *                singular point block (|det| outside 1e-300..1e300, as for a point whose observations are all inactive): its inverse
+ *                is the zero block, so its dp is 0, not NaN, and it adds nothing to S.   iters_host: the iterations run.
+ *
+ * Errors (SFM_ERR_ARG / SFM_ERR_WORKSPACE, before any device call): sizes outside the limits above, mode outside 0..1, huber NaN or
+ *   <= 0, lam, cg_tol or cg_iters negative, NULL where the count is non-zero (the CSR offsets, cams, K, X, the blocks, stat, count,
+ *   in, out, dc, dp and the workspace always), a workspace smaller than sfm_track_ba_ws_bytes says (0 for invalid sizes; 160 bytes
+ *   per observation for the rows, 216 per chunk, the step's vectors).
+ * ---------------------------------------------------------------------- */
+size_t sfm_track_ba_ws_bytes(int64_t ncam, int64_t npt, int64_t nobs);
+int sfm_track_ba_sweep(const double* cams_dev, int64_t ncam, const double* K_host, const double* X_dev, int64_t npt, const float* obs_dev,
+                       const int32_t* track_off_dev, const int32_t* cam_idx_dev, const int32_t* pt_idx_dev, const int32_t* cam_off_dev,
+                       const int32_t* cam_obs_dev, int64_t nobs, double huber, int mode, uint8_t* active_dev, double* JtJ_cam_dev,
+                       double* Jtr_cam_dev, double* JtJ_pt_dev, double* Jtr_pt_dev, double* stat_dev, int32_t* count_dev, void* ws_dev,
+                       size_t ws_bytes, void* stream);
+int sfm_track_ba_product(int64_t ncam, int64_t npt, const int32_t* track_off_dev, const int32_t* cam_idx_dev, const int32_t* pt_idx_dev,
+                         const int32_t* cam_off_dev, const int32_t* cam_obs_dev, int64_t nobs, int mode, const double* in_dev, double* out_dev,
+                         void* ws_dev, size_t ws_bytes, void* stream);
+int sfm_track_ba_step(int64_t ncam, int64_t npt, const int32_t* track_off_dev, const int32_t* cam_idx_dev, const int32_t* pt_idx_dev,
+                      const int32_t* cam_off_dev, const int32_t* cam_obs_dev, int64_t nobs, const double* JtJ_cam_dev, const double* Jtr_cam_dev,
+                      const double* JtJ_pt_dev, const double* Jtr_pt_dev, double lam, int fix_first_camera, double cg_tol, int cg_iters,
+                      double* dc_dev, double* dp_dev, int32_t* iters_host, int32_t* status_host, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

@@ -123,6 +123,12 @@ SIGNATURES = {
                                 _vp, _vp, _sz, _vp]),
     "sfm_track_prune_ws_bytes": (_sz, [_i64]),
     "sfm_track_prune": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_ba_ws_bytes": (_sz, [_i64, _i64, _i64]),
+    "sfm_track_ba_sweep": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _sz, _vp]),
+    "sfm_track_ba_product": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_ba_step": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _int, _f64, _int, _vp, _vp,
+                                 _c.POINTER(_i32), _c.POINTER(_i32), _vp, _sz, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

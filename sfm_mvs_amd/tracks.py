@@ -6,7 +6,8 @@ orders them, `triangulate_tracks` triangulates each from all its views.  All fou
 for the host; `run_tracks` composes them, reads the counts once and downloads once, and returns the points and observations in the
 form `ba.bundle_adjust_schur(cams, K, X, obs, cam_idx, pt_idx)` takes.  `refine_tracks` and `prune_tracks` ("TRACKS-REFINE";
 docs/tracks.md §8) refine each point under a Huber loss, flag observations one by one and keep a track with its inliers only:
-`run_tracks(robust=True)`."""
+`run_tracks(robust=True)`.  `adjust_tracks` ("TRACKS-BA"; docs/tracks.md §9) bundle-adjusts what `run_tracks` returned and gives back
+the camera matrices `run_tracks` takes."""
 import numpy as np
 import torch
 
@@ -320,6 +321,23 @@ def _robust_result(host_head, lowered, pruned, img_off, kp):
                 obs=np.ascontiguousarray(host[pos[3]:].view(np.float32).reshape(nobs, 2)), cam_idx=np.ascontiguousarray(host[pos[2]:pos[3]]),
                 pt_idx=np.repeat(np.arange(T), length).astype(np.int32), track_len=length.astype(np.int32), counts=host_head[:6].copy(),
                 status=np.array([int(host_head[6]), lowered], np.int32), tracks_dropped=int(host_head[10]), obs_dropped=int(host_head[11]))
+
+
+def adjust_tracks(result, P, K, device=None, **kw):
+    """Bundle adjustment of the tracks `run_tracks` returned (either variant) from the cameras P [n_img, 3, 4] it was given, K 3 x 3:
+    `track_ba.bundle_adjust_tracks(cams_from_P(P, K), K, points, obs, cam_idx, pt_idx, **kw)` (huber, iters, lam, fix_first_camera,
+    cg_tol, cg_iters, log).  Returns (P' [n_img, 3, 4] float64, points' [T, 3] float64, info) on the host; info holds the history of
+    robust costs and the counts of the last sweep.  `run_tracks(..., P')` then runs on the adjusted cameras."""
+    from . import track_ba
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    cams0 = track_ba.cams_from_P(P, K)
+    cams, X, hist, info = track_ba.bundle_adjust_tracks(_upload(cams0, dev), K, _upload(np.asarray(result["points"], np.float64).reshape(-1, 3), dev),
+                                                        _upload(np.asarray(result["obs"], np.float32).reshape(-1, 2), dev),
+                                                        _upload(np.asarray(result["cam_idx"], np.int32), dev),
+                                                        _upload(np.asarray(result["pt_idx"], np.int32), dev), **kw)
+    host = torch.cat([cams.reshape(-1), X.reshape(-1)]).cpu().numpy()
+    info = dict(info, history=hist)
+    return track_ba.P_from_cams(host[:cams.numel()].reshape(-1, 6), K), host[cams.numel():].reshape(-1, 3).copy(), info
 
 
 def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70):
