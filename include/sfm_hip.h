@@ -1173,6 +1173,65 @@ int sfm_track_ba_step(int64_t ncam, int64_t npt, const int32_t* track_off_dev, c
                       const double* JtJ_pt_dev, const double* Jtr_pt_dev, double lam, int fix_first_camera, double cg_tol, int cg_iters,
                       double* dc_dev, double* dp_dev, int32_t* iters_host, int32_t* status_host, void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * MVS-PLAN (no reference counterpart; csrc/mvs_plan.hip, docs/mvs.md §8): the sources and the depth range of every view of the plane
+ * sweep from the sparse model, i.e. from the point-major observations of TRACKS-BA's problem layout (track_off_dev [npt + 1], cam_idx_dev,
+ * pt_idx_dev [nobs], cam_off_dev [ncam + 1], cam_obs_dev [nobs]), X_dev FLOAT64 [npt][3] and P_dev float64 [ncam][12].
+ *   1 <= ncam <= 4096, 0 <= npt <= 2^31-1, 0 <= nobs <= 2^31-1, 1 <= nsrc <= SFM_PLAN_MAX_SRC = 8 (mvs.MAX_VIEWS).
+ *   No index is trusted: a CSR row is clamped to 0 <= lo <= hi <= nobs; an observation whose cam_idx is outside 0..ncam-1 takes part in
+ *   no pair; an entry of cam_obs outside 0..nobs-1, or naming an observation whose cam_idx is not the row's camera or whose pt_idx is
+ *   outside 0..npt-1, has no depth.  Every read and write stays inside the arrays.  No entry point waits for the host and none takes a
+ *   workspace.  Every output word is a count, a rank, a copy or an order statistic: the integer atomics of csrc/mvs_plan.hip commute,
+ *   THERE ARE NO FLOATING-POINT ATOMICS, and a second run gives the same bits.
+ *
+ * sfm_view_pair_counts — shared_dev, good_dev int32 [ncam][ncam], symmetric, zero diagonal (counts modulo 2^32); C_dev float64 [ncam][3].
+ *   centres    C_dev is WRITTEN by a small kernel of the same call (the cosines depend on the centres to the bit, so they come from one
+ *              stated formula, and P is what callers hold), by adjugate over determinant as sfm_track_refine's centres:
+ *                a00 = p5 * p10 - p6 * p9;  a01 = p2 * p9 - p1 * p10;  a02 = p1 * p6 - p2 * p5
+ *                a10 = p6 * p8 - p4 * p10;  a11 = p0 * p10 - p2 * p8;  a12 = p2 * p4 - p0 * p6
+ *                a20 = p4 * p9 - p5 * p8;   a21 = p1 * p8 - p0 * p9;   a22 = p0 * p5 - p1 * p4
+ *                det = (p0 * a00 + p1 * a10) + p2 * a20;   C_r = -(((ar0 * p3 + ar1 * p7) + ar2 * p11) / det)
+ *   shared     every pair p < q of the observations of one track (row t of track_off) whose cameras a = cam_idx[p], b = cam_idx[q] are
+ *              both in 0..ncam-1 and differ adds 1 to shared[a][b] and to shared[b][a].
+ *   good       the same pair also adds 1 to good[a][b] and good[b][a] iff X[t] is finite in its three components and, with the rays
+ *              r = X[t] - C[a], s = X[t] - C[b] (component by component), n_r = (r0 * r0 + r1 * r1) + r2 * r2, n_s likewise,
+ *                c = ((r0 * s0 + r1 * s1) + r2 * s2) / sqrt(n_r * n_s)
+ *              (the order of cos_min in sfm_track_refine) satisfies cos_lo <= c <= cos_hi; a NaN c fails.  There is no acos on the
+ *              device: callers pass cosines (cos_lo = cos(max angle), cos_hi = cos(min angle)).
+ *   kernels    SFM_PLAN_GROUP = 16 lanes per track; the rays of a track are computed once per tile of 64 observations and kept in LDS.
+ *              While ncam <= SFM_PLAN_LDS_CAMS = 96 a workgroup counts in LDS (two upper triangles of int32: 36 480 bytes at 96, with the
+ *              36 KiB of ray tiles two workgroups per CU of 160 KiB) and flushes one global atomic per non-zero cell; above it every
+ *              contribution is a global atomic.  A last kernel mirrors the upper triangles.
+ *
+ * sfm_view_depth_ranges — m_dev int32 [ncam], z_lo_dev, z_hi_dev float32 [ncam].
+ *   depth      of entry k of camera i's row (o = cam_obs[k], j = pt_idx[o]):  z = (float)(((P8 * X[j]0 + P9 * X[j]1) + P10 * X[j]2) + P11)
+ *              with P = P_dev[i], in float64 and rounded once; VALID iff it is finite and > 0 (denormals are valid).
+ *   m          the number of valid depths of the camera.
+ *   z_lo, z_hi the valid depths of rank floor(lo_permille * (m - 1) / 1000) and ceil(hi_permille * (m - 1) / 1000) in ascending order
+ *              (int64 arithmetic): order statistics, what np.sort gives, ties included; not interpolated.  m == 0 writes 0, 0.
+ *   kernel     one workgroup per camera; a radix select over the uint32 views of the depths, four passes of 8 bits with both ranks at once,
+ *              histograms in LDS.  The depths are recomputed in every pass: rows that overlap cannot race and there is no workspace.
+ *
+ * sfm_view_select — nbr_dev int32 [ncam][nsrc], n_nbr_dev int32 [ncam].
+ *   For view i the views j != i with good[i][j] >= min_good (>= 0), ordered by good[i][j] descending, then shared[i][j] descending, then j
+ *   ascending: the first nsrc of them, then -1; n_nbr[i] = how many were written.  One wave per view, nsrc rounds over the row.
+ *
+ * Errors (SFM_ERR_ARG, before any device call): sizes outside the limits above, a NaN cosine bound, permille bounds that are not
+ *   0 <= lo <= hi <= 1000, nsrc outside 1..8, a negative min_good, NULL where the count is non-zero (the CSR offsets, P, C and the
+ *   outputs always).
+ * ---------------------------------------------------------------------- */
+#define SFM_PLAN_GROUP 16
+#define SFM_PLAN_LDS_CAMS 96
+#define SFM_PLAN_MAX_SRC 8
+int sfm_view_pair_counts(const int32_t* track_off_dev, const int32_t* cam_idx_dev, const double* X_dev, int64_t npt, int64_t nobs,
+                         const double* P_dev, int64_t ncam, double cos_lo, double cos_hi, double* C_dev, int32_t* shared_dev, int32_t* good_dev,
+                         void* stream);
+int sfm_view_depth_ranges(const int32_t* cam_off_dev, const int32_t* cam_obs_dev, const int32_t* cam_idx_dev, const int32_t* pt_idx_dev,
+                          int64_t nobs, const double* X_dev, int64_t npt, const double* P_dev, int64_t ncam, int lo_permille, int hi_permille,
+                          int32_t* m_dev, float* z_lo_dev, float* z_hi_dev, void* stream);
+int sfm_view_select(const int32_t* shared_dev, const int32_t* good_dev, int64_t ncam, int nsrc, int min_good, int32_t* nbr_dev,
+                    int32_t* n_nbr_dev, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

@@ -74,6 +74,9 @@ def neighbours(i, n, nsrc=4):
     return out
 
 
+_sequence_neighbours = neighbours       # run_mvs has a keyword of that name
+
+
 def _relative(K, P_ref, P_other):
     """(G, g): the pixel of the reference at depth d maps to d*(G x~) + g in the other camera (homogeneous, its z the camera
     depth there): G = K R_o R_r^T K^-1, g = K (t_o - R_o R_r^T t_r)."""
@@ -266,8 +269,40 @@ P1 = 10             # a change of one plane between neighbouring pixels
 P2 = 102            # any larger change
 
 
+def _checked_neighbours(nbrs, n):
+    """run_mvs's `neighbours` keyword as a list of lists of ints, or an SfmHipError: one list per view, at most MAX_VIEWS entries, each
+    an index in 0..n-1 other than the view's own."""
+    if len(nbrs) != n:
+        raise SfmHipError(f"run_mvs: neighbours holds {len(nbrs)} lists for {n} cameras")
+    out = []
+    for i, row in enumerate(nbrs):
+        row = list(row)
+        if len(row) > MAX_VIEWS:
+            raise SfmHipError(f"run_mvs: view {i} names {len(row)} neighbours, more than MAX_VIEWS = {MAX_VIEWS}")
+        for v in row:
+            if isinstance(v, (bool, float, np.floating)) or int(v) != v or not 0 <= int(v) < n:
+                raise SfmHipError(f"run_mvs: neighbour {v!r} of view {i} is not a view index in 0..{n - 1}")
+            if int(v) == i:
+                raise SfmHipError(f"run_mvs: view {i} names itself as a neighbour")
+        out.append([int(v) for v in row])
+    return out
+
+
+def _checked_ranges(ranges, n, ndepth):
+    """run_mvs's `ranges` keyword as the float32 [n, ndepth] plane inverse depths, or an SfmHipError: one finite 0 < dmin < dmax per view."""
+    try:
+        r = np.asarray(ranges, np.float64)
+    except (TypeError, ValueError) as e:
+        raise SfmHipError("run_mvs: ranges must hold one (dmin, dmax) per view") from e
+    if r.shape != (n, 2):
+        raise SfmHipError(f"run_mvs: ranges has shape {r.shape}, not ({n}, 2)")
+    if not np.all(np.isfinite(r)) or not np.all((r[:, 0] > 0) & (r[:, 0] < r[:, 1])):
+        raise SfmHipError("run_mvs: every range needs finite 0 < dmin < dmax")
+    return np.stack([_inverse_depths_host(a, b, ndepth) for a, b in r])
+
+
 def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_min=VAR_MIN, cost_max=COST_MAX, tau=0.01,
-            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8):
+            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8, neighbours=None, ranges=None):
     """Dense reconstruction of a registered sequence: a plane-sweep depth map per view, geometric-consistency filtering, and one
     coloured cloud.
 
@@ -281,6 +316,12 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     aggregate: True replaces every view's winner-take-all depth map by aggregate_depth of the sweep's cost volume (shiftable
              windows of half-width `shift`, None = radius; semi-global penalties p1 / p2 over `ndir` directions): docs/mvs.md §7.
              The float volume, Q and S are allocated once and reused by every view (10 bytes per pixel and plane).
+    neighbours: None, or per view the list of its source views (at most MAX_VIEWS, none the view itself) instead of the sequence
+             neighbours, e.g. `mvs_plan.host_plan(...)["neighbours"]` for frames in any order (docs/mvs.md §8).  The length of a view's
+             list caps topk and min_consistent for that view; a view with an empty list gets an all-zero depth map, no sweep, and
+             contributes no point.
+    ranges:  None, or per view (dmin, dmax) of its planes instead of depth_range(Xtot, P_i) (Xtot is then not read).
+             Both are validated before any launch.
     Returns dict(depths [per view (H, W) float32 device tensor], points (m, 3) float64, colors (m, 3) float64 B G R): shaped as
     Xtot / colorstot, so that pipeline.to_ply(path, points, colors, densify=True) writes Point_Cloud/dense.ply.
     One host wait per call: the fused point count (then one download of the points and colours); every upload is stream-ordered
@@ -296,6 +337,8 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
         raise SfmHipError("run_mvs: needs at least two registered views")
     nsrc = min(int(nsrc), n - 1, MAX_VIEWS)
     topk = min(int(topk), nsrc)
+    nbrs = [_sequence_neighbours(i, n, nsrc) for i in range(n)] if neighbours is None else _checked_neighbours(neighbours, n)
+    planes = None if ranges is None else _checked_ranges(ranges, n, ndepth)
     dev = torch.device("cuda", torch.cuda.current_device())
     if all(torch.is_tensor(im) and im.is_cuda for im in images):
         frames = [im.to(dev).contiguous() for im in images]
@@ -308,25 +351,30 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
         raise SfmHipError("run_mvs: frames must be (H, W, 3) uint8 BGR of one size")
     h, w = frames[0].shape[:2]
     grays = [bgr2gray(f) for f in frames]
-    nbrs = [neighbours(i, n, nsrc) for i in range(n)]
     # every view's planes in one upload, before the first launch (a per-view upload would wait for the previous view's sweep)
-    invd = _upload(np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)]), dev)
+    invd = _upload(np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)]) if planes is None else planes, dev)
     depths = []
     if aggregate:
         vol = torch.empty((int(ndepth), h, w), dtype=torch.float32, device=dev)
         qbuf = torch.empty((int(ndepth), h, w), dtype=torch.uint16, device=dev)
         sbuf = torch.empty((int(ndepth), h, w), dtype=torch.uint16, device=dev)
     for i in range(n):
+        if not nbrs[i]:                                         # no source: no sweep, an all-zero map
+            depths.append(torch.zeros((h, w), dtype=torch.float32, device=dev))
+            continue
         mv = sweep_matrices(K, Ps[i], Ps[nbrs[i]])
         if aggregate:
-            plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, topk, var_min, cost_max, volume_out=vol)
+            plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, min(topk, len(nbrs[i])), var_min, cost_max, volume_out=vol)
             d, _, _ = aggregate_depth(vol, invd[i], radius if shift is None else shift, p1, p2, ndir, cost_max, q_out=qbuf, s_out=sbuf)
         else:
-            d, _, _, _ = plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, topk, var_min, cost_max)
+            d, _, _, _ = plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, min(topk, len(nbrs[i])), var_min, cost_max)
         depths.append(d)
     masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
     for i in range(n):
+        if not nbrs[i]:
+            masks[i].zero_()
+            continue
         ab, bc = consistency_matrices(K, Ps[i], Ps[nbrs[i]])
         consistency(depths[i], [depths[v] for v in nbrs[i]], nbrs[i], ab, i, bc, tau, min(int(min_consistent), len(nbrs[i])), unique,
                     mask_out=masks[i], xyz_out=xyz[i])

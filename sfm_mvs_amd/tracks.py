@@ -7,7 +7,8 @@ for the host; `run_tracks` composes them, reads the counts once and downloads on
 form `ba.bundle_adjust_schur(cams, K, X, obs, cam_idx, pt_idx)` takes.  `refine_tracks` and `prune_tracks` ("TRACKS-REFINE";
 docs/tracks.md §8) refine each point under a Huber loss, flag observations one by one and keep a track with its inliers only:
 `run_tracks(robust=True)`.  `adjust_tracks` ("TRACKS-BA"; docs/tracks.md §9) bundle-adjusts what `run_tracks` returned and gives back
-the camera matrices `run_tracks` takes."""
+the camera matrices `run_tracks` takes.  `densify_tracks` ("MVS-PLAN"; docs/mvs.md §8) plans every view's sources and depth range from
+the tracks and runs `mvs.run_mvs` with them: the frames may come in any order."""
 import numpy as np
 import torch
 
@@ -338,6 +339,29 @@ def adjust_tracks(result, P, K, device=None, **kw):
     host = torch.cat([cams.reshape(-1), X.reshape(-1)]).cpu().numpy()
     info = dict(info, history=hist)
     return track_ba.P_from_cams(host[:cams.numel()].reshape(-1, 6), K), host[cams.numel():].reshape(-1, 3).copy(), info
+
+
+def densify_tracks(result, images, K, P, points=None, nsrc=4, min_angle_deg=None, max_angle_deg=None, min_good=None, lo=2, hi=98, device=None, **kw):
+    """Dense reconstruction of the views of a `run_tracks` result (either variant): `track_ba.plan` -> `mvs_plan.plan_views` ->
+    `mvs_plan.host_plan` -> `mvs.run_mvs(images, K, posearr, points, neighbours=..., ranges=..., **kw)`.  P [n_img, 3, 4] float64 and
+    `points` (default result["points"]; pass the float64 points `adjust_tracks` returned with its P') are the cameras and the cloud the
+    plan is made from; the angle window and min_good default to mvs_plan's.  Returns run_mvs's dict plus "plan" (host_plan's dict).
+    Host waits: host_plan's one, then run_mvs's."""
+    from . import mvs, mvs_plan, track_ba
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    P = np.ascontiguousarray(np.asarray(P, np.float64).reshape(-1, 3, 4))
+    X = np.ascontiguousarray(np.asarray(result["points"] if points is None else points, np.float64).reshape(-1, 3))
+    pl = track_ba.plan(_upload(np.asarray(result["cam_idx"], np.int32), dev), _upload(np.asarray(result["pt_idx"], np.int32), dev), len(P), len(X))
+    planned = mvs_plan.plan_views(pl, _upload(X, dev), _upload(P, dev), nsrc,
+                                  mvs_plan.MIN_ANGLE_DEG if min_angle_deg is None else min_angle_deg,
+                                  mvs_plan.MAX_ANGLE_DEG if max_angle_deg is None else max_angle_deg,
+                                  mvs_plan.MIN_GOOD if min_good is None else min_good, lo, hi)
+    hp = mvs_plan.host_plan(planned)
+    posearr = np.concatenate([K.ravel(), P.ravel()])
+    out = mvs.run_mvs(images, K, posearr, X, nsrc=nsrc, neighbours=hp["neighbours"], ranges=hp["ranges"], **kw)
+    out["plan"] = hp
+    return out
 
 
 def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70):
