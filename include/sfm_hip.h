@@ -1232,6 +1232,83 @@ int sfm_view_depth_ranges(const int32_t* cam_off_dev, const int32_t* cam_obs_dev
 int sfm_view_select(const int32_t* shared_dev, const int32_t* good_dev, int64_t ncam, int nsrc, int min_good, int32_t* nbr_dev,
                     int32_t* n_nbr_dev, void* stream);
 
+/* ------------------------------------------------------------------------
+ * TRACKS-REGISTER (no reference counterpart; csrc/tracks_register.hip, docs/tracks.md §10): the bookkeeping of track-driven incremental
+ * registration.  The FULL table is what sfm_track_build leaves: counts_dev int32 [>= 2] = (T, nobs), track_off_dev int32 [N / 2 + 2],
+ * obs_node_dev int32 [N], node_track_dev int32 [N], with img_off_dev int32 [n_img + 1] and kp_dev float32 [N][2] of TRACKS;
+ * N = n_nodes in 0..2^31-1, n_img in 1..65 536.
+ *   counts     every counts array is read on the device and clamped as sfm_track_prune clamps it: T to 0..N / 2 + 1, nobs to 0..N (a value
+ *              outside becomes the upper end); a track's range is lo = min(max(track_off[t], 0), nobs), hi = min(max(track_off[t + 1],
+ *              lo), nobs).
+ *   image of a node u: the largest i < n_img with img_off[i] <= u (a binary search of at most 17 steps; its result lies in 0..n_img-1
+ *              whatever img_off holds).
+ *   Every output word is a count, a rank, a bit-or or a copy: no word depends on the order in which atomics land (the only atomics are
+ *   the integer add and or of sfm_track_view_scores).  Nothing at or past the counted rows is written.  Every read and write stays
+ *   inside the arrays for garbage counts, nodes outside 0..N-1 and offsets in no order (the outputs are then unspecified); every loop
+ *   is bounded.  No entry point waits for the host.
+ *
+ * sfm_track_restrict — registered_dev uint8 [n_img], min_len in 1..2^31-1.  Observation o is LIVE iff its node obs_node[o] lies in 0..N-1
+ *   and registered[image of the node] != 0.  Track t < T is KEPT iff it has at least min_len live observations.  Kept tracks in ascending
+ *   old order are tracks 0..T2-1 and hold their live observations in the old order: track_off2_dev int32 [N / 2 + 2] (T2 + 1 words
+ *   written), obs_node2_dev int32 [N] (nobs2 words), track_src_dev int32 [N / 2 + 1] (the old index, T2 words), counts2_dev int32 [4] =
+ *   (T2, nobs2, tracks with 1..min_len-1 live observations, non-live observations of kept tracks).  Ranks come from per-block counts and
+ *   a one-workgroup scan; no atomics.  (counts2, track_off2, obs_node2) have the shape sfm_track_build leaves: sfm_track_triangulate,
+ *   sfm_track_refine and sfm_track_prune run on them unchanged, and since every observation left lies in a registered image they never
+ *   read a row of P_dev that belongs to an unregistered one.
+ *
+ * sfm_track_adopt — composes two compactions of the full table: counts_r_dev / track_src_r_dev are the counts2 / track_src that
+ *   sfm_track_restrict wrote, counts_p_dev / track_off_p_dev / obs_node_p_dev / X_p_dev / track_src_p_dev the counts2 / track_off2 /
+ *   obs_node2 / X2 / track_src that sfm_track_prune wrote on the (triangulated, refined) restricted table.  Pruned track p <
+ *   Tp is ADOPTED by t = track_src_r[r], r = track_src_p[p], when r lies in 0..Tr-1 and t in 0..T-1.
+ *   X_full_dev float32 [N / 2 + 1][3], has_point_dev uint8 [N / 2 + 1]: every row t < T is rewritten by every call: 1 and the words of
+ *              X_p[p] for an adopted track, 0 and three quiet NaNs 0x7FC00000 for any other.
+ *   obs_live_dev uint8 [N]: every row o < nobs is rewritten: for an adopted track, with j starting at the first observation of p, the
+ *              observations o of t in ascending order: when j is before the end of p and obs_node[o] == obs_node_p[j], obs_live[o] = 1
+ *              and j advances; every other row is 0.  (Both compactions keep the old order, so the list of p is a subsequence of the
+ *              list of t and obs_live marks exactly the observations that survived both.)
+ *
+ * sfm_track_view_scores — has_point_dev as sfm_track_adopt wrote it; one frame size (width, height), finite and > 0; grid in 1..8.
+ *   Node u in 0..N-1 COUNTS iff t = node_track[u] lies in 0..T-1 and has_point[t] != 0.  For every image i:
+ *   seen_dev   int32 [n_img]: the nodes that count and whose image is i.
+ *   cover_dev  uint64 [n_img]: the OR of the bits 1 << (cy * grid + cx) over those nodes, with, in float32,
+ *                sx = (float)grid / (float)width;  sy = (float)grid / (float)height   (one division each, on the host)
+ *                cx = cell(kp[u][0] * sx);  cy = cell(kp[u][1] * sy)
+ *                cell(c) = NONE when c is NaN, 0 when c < 0, grid - 1 when c >= grid, else (int)c (towards zero)
+ *              so keypoints outside the frame fall into the border cell.  A node with a NaN coordinate counts in seen and sets NO bit.
+ *   cells_dev  int32 [n_img]: the number of set bits of cover.
+ *   Registered images are scored like any other.  One lane per node; while n_img <= SFM_REGISTER_LDS_IMAGES = 256 a workgroup keeps its
+ *   counters and masks in LDS (3 072 bytes) and flushes one global atomic add and or per non-zero entry; above it every node is one
+ *   global atomic add and at most one 64-bit atomic or.
+ *
+ * sfm_track_correspondences — for image `image` in 0..n_img-1 and its nodes u in [min(max(img_off[image], 0), N), min(max(img_off[image +
+ *   1], lo), N)) in ascending order, each node that counts (as above) is a row k: X_out_dev float32 [capacity][3] = the words of
+ *   X_full[t], uv_out_dev float32 [capacity][2] = the words of kp[u], track_out_dev int32 [capacity] = t; count_dev int32 [1] = the
+ *   number of rows, which equals seen[image].  Rows at or past min(count, capacity) are not written.  Ranks by per-block counts and a
+ *   one-workgroup scan; no atomics.  X_out and uv_out are what sfm_solve_pnp_ransac takes.
+ *
+ * Errors (SFM_ERR_ARG, before any device call): n_nodes or capacity outside 0..2^31-1, n_img outside 1..65 536, min_len outside
+ *   1..2^31-1, grid outside 1..8, a frame size that is NaN, infinite or <= 0, image outside 0..n_img-1, NULL where the count is non-zero
+ *   (counts, offsets, per-track and per-image arrays and the workspaces always), a workspace smaller than the _ws_bytes twin says.  The
+ *   _ws_bytes twins return 0 for invalid sizes.
+ * ---------------------------------------------------------------------- */
+#define SFM_REGISTER_LDS_IMAGES 256
+size_t sfm_track_restrict_ws_bytes(int64_t n_nodes);
+int sfm_track_restrict(const int32_t* counts_dev, const int32_t* track_off_dev, const int32_t* obs_node_dev, const int32_t* img_off_dev,
+                       int n_img, int64_t n_nodes, const uint8_t* registered_dev, int64_t min_len, int32_t* track_off2_dev,
+                       int32_t* obs_node2_dev, int32_t* track_src_dev, int32_t* counts2_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int sfm_track_adopt(const int32_t* counts_dev, const int32_t* track_off_dev, const int32_t* obs_node_dev, int64_t n_nodes,
+                    const int32_t* counts_r_dev, const int32_t* track_src_r_dev, const int32_t* counts_p_dev, const int32_t* track_off_p_dev,
+                    const int32_t* obs_node_p_dev, const float* X_p_dev, const int32_t* track_src_p_dev, float* X_full_dev,
+                    uint8_t* has_point_dev, uint8_t* obs_live_dev, void* stream);
+int sfm_track_view_scores(const int32_t* counts_dev, const int32_t* node_track_dev, const uint8_t* has_point_dev, const int32_t* img_off_dev,
+                          int n_img, const float* kp_dev, int64_t n_nodes, double width, double height, int grid, int32_t* seen_dev,
+                          uint64_t* cover_dev, int32_t* cells_dev, void* stream);
+size_t sfm_track_correspondences_ws_bytes(int64_t n_nodes);
+int sfm_track_correspondences(int image, const int32_t* counts_dev, const int32_t* node_track_dev, const uint8_t* has_point_dev,
+                              const float* X_full_dev, const int32_t* img_off_dev, int n_img, const float* kp_dev, int64_t n_nodes,
+                              int64_t capacity, float* X_out_dev, float* uv_out_dev, int32_t* track_out_dev, int32_t* count_dev, void* ws_dev,
+                              size_t ws_bytes, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

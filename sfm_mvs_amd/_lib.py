@@ -132,6 +132,12 @@ SIGNATURES = {
     "sfm_view_pair_counts": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "sfm_view_depth_ranges": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "sfm_view_select": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "sfm_track_restrict_ws_bytes": (_sz, [_i64]),
+    "sfm_track_restrict": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_adopt": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_track_view_scores": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _i64, _f64, _f64, _int, _vp, _vp, _vp, _vp]),
+    "sfm_track_correspondences_ws_bytes": (_sz, [_i64]),
+    "sfm_track_correspondences": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),
