@@ -1309,6 +1309,77 @@ int sfm_track_correspondences(int image, const int32_t* counts_dev, const int32_
                               int64_t capacity, float* X_out_dev, float* uv_out_dev, int32_t* track_out_dev, int32_t* count_dev, void* ws_dev,
                               size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * VERIFY (no reference counterpart: isfm.py:73-94 verifies one pair at a time; csrc/verify.hip, docs/tracks.md section 11): geometric
+ * verification of ALL pairs of a match store in six launches (the last three once per chunk of pairs in verify.verify_pairs) and no host wait: a fixed budget of H five-point hypotheses per pair
+ * from a counter-based sampler, all scored, the best decomposed and voted on.  A new algorithm, not a restatement of the sequential
+ * RANSAC of sfm_find_essential_mat: the masks differ from the per-pair path's.  Every integer output is a count, a rank, a maximum of
+ * a key or a copy; every float64 operation is correctly rounded in the order written (no FMA, IEEE / and sqrt; only + - * / sqrt
+ * fabs fmax and comparisons are used).  tests/np_verify.py restates every output word.  store, pair_img, nq, img_off, nodes: as TRACKS.
+ *
+ * sfm_verify_normalise — once per node: xn[u] = ((double)kp[u].x * ifx + bx, (double)kp[u].y * ify + by) with ifx = 1 / K[0],
+ *   bx = -K[2] * (1 / K[0]), ify = 1 / K[4], by = -K[5] * (1 / K[4]) (K_host: 9 doubles, row-major).  xn_dev float64 [n_nodes][2].
+ *
+ * sfm_verify_survivors — pair p = (i, j) with i != j and both in 0..n_img-1: the queries q < min(nq[p], cap, size of i), in ascending q,
+ *   that pass the survivor rule of sfm_match_edges without keep (trainIdx0 = t in 0..size of j - 1, trainIdx1 >= 0,
+ *   (double)d0 < ratio * (double)d1).  surv_dev int32 [n_pairs][cap][2]: the survivors as (q, t), then (-1, -1) up to cap.
+ *   m_dev int32 [n_pairs]: their number; 0 for every other pair.
+ *
+ * sfm_verify_samples — samp_dev int32 [n_pairs][H][5], H = budget in 1..1024.  In uint32 arithmetic
+ *     mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *     draw c of sample s of pair p:  h = mix(mix(mix(seed + 0x9e3779b9 * p) ^ s) + c);  idx = ((uint64)h * m) >> 32     (m = m_dev[p])
+ *   the five slots take, for c = 0, 1, 2, .. 63, the first draws that differ from every slot filled before.  A sample that 64 draws do
+ *   not fill, and every sample of a pair with m < 5, is five times -1.
+ *
+ * sfm_verify_models — one lane per sample.  With m' = min(m, cap): a sample is VALID when both images are in range, m' >= 5, every
+ *   slot is in 0..m'-1 and both nodes (img_off[i] + q, img_off[j] + t) of its survivors lie in 0..n_nodes-1.  A valid sample runs the
+ *   operations of sfm_host_five_point (csrc/host_solvers.h: cv::SVD of the 5 x 9 system with FULL_UV, the ten cubic constraints,
+ *   elimination with partial pivoting, det B(z), cv::solvePoly with 300 sweeps, one 3 x 3 SVD per real root) in the same order on
+ *   x1 = xn of the five first nodes, x2 = xn of the five second nodes, and returns the same bits.
+ *   nmodels_dev int32 [n_pairs][H]: 0..10 (0 for an invalid sample); E_dev float64 [n_pairs][H][10][9]: the unit-norm matrices,
+ *   zero past nmodels.  E_dev is the workspace of the family: n_pairs * H * 720 bytes.
+ *
+ * sfm_verify_score — a model is (p, s, j) with j < nmodels[p][s] (clamped to 0..10); its slot is 10 s + j.  Over the first
+ *   m' = min(m, cap) survivors of the pair whose two nodes lie in 0..n_nodes-1 (m' = 0 when an image is out of range), with
+ *   (a1, b1) = xn of the first node, (a2, b2) of the second, residual.hip's score_essential_kernel word for word:
+ *     e0 = E0 a1 + E1 b1 + E2 * 1;  e1 = E3 a1 + E4 b1 + E5 * 1;  e2 = E6 a1 + E7 b1 + E8 * 1      (left to right)
+ *     f0 = E0 a2 + E3 b2 + E6 * 1;  f1 = E1 a2 + E4 b2 + E7 * 1;  s = a2 e0 + b2 e1 + 1 * e2
+ *     inlier  <=>  (float)(s * s / (((e0 e0 + e1 e1) + f0 f0) + f1 f1)) <= thr2
+ *   counts_dev int32 [n_pairs][H][10]: the inlier count of every model, 0 in every other slot.
+ *   best_dev uint64 [n_pairs]: the maximum over the pair's models of (count << 32) | (0xFFFFFFFF - slot): the largest count, then the
+ *   smallest sample, then the smallest model index; 0 for a pair without a model.
+ *
+ * sfm_verify_select — per pair.  Without a model (best = 0, or a slot >= 10 H): keep row, E and Rt zero, info = (m, scored, 0, 0, -1,
+ *   -1, -1, status).  Otherwise E = the model of the best slot; its Sampson inliers as above (a survivor with q >= cap is none);
+ *   (R1, R2, t) = the operations of sfm_host_decompose_essential; the candidates c = 0..3 are [R1 | t], [R2 | t], [R1 | -t], [R2 | -t]
+ *   (3 x 4 row-major); over the Sampson inliers the vote of sfm_recover_pose_score with rows = 4 and dist_thresh = 50 (the DLT of
+ *   [I | 0] and the candidate on (a1, b1), (a2, b2), cv::SVD's one-sided Jacobi, Q2 Q3 > 0, Q2 / Q3 < 50, 0 < z' < 50).  The winner
+ *   is the candidate with the most votes, the lowest c on ties.
+ *   keep_dev uint8 [n_pairs][cap]: 1 at the queries q of the Sampson inliers that pass the winner's vote, 0 in every other column.
+ *   E_out_dev float64 [n_pairs][9], Rt_dev float64 [n_pairs][12] (the winning candidate).
+ *   info_dev int32 [n_pairs][8]: survivors m (as given), models scored (the sum of nmodels), Sampson inliers, inliers that pass the
+ *   winner's vote, best sample, best model index, winning candidate, status bits (1: m < 5, 2: no model, 4: the winner has no vote).
+ *
+ * thr2 is (float)(thr * thr), thr = threshold / ((K[0] + K[4]) / 2), computed by the caller as sfm_find_essential_mat computes it.
+ * Errors (SFM_ERR_ARG, before any device call): negative sizes, n_pairs * cap or n_nodes above 2^31 - 1, n_pairs above (2^31 - 1) / 1024
+ *   (samples, models) or above (2^31 - 1) / 10 240 (score, select), whatever the budget, n_img outside 1..65 536, a NaN ratio, budget outside 1..1024, NULL where the count is non-zero (K_host and img_off_dev always).
+ * ---------------------------------------------------------------------- */
+#define SFM_VERIFY_MAX_BUDGET 1024
+int sfm_verify_normalise(const float* kp_dev, int64_t n_nodes, const double* K_host, double* xn_dev, void* stream);
+int sfm_verify_survivors(const int32_t* store_dev, int64_t n_pairs, int64_t cap, const int32_t* pair_img_dev, const int32_t* nq_dev,
+                         const int32_t* img_off_dev, int n_img, double ratio, int32_t* surv_dev, int32_t* m_dev, void* stream);
+int sfm_verify_samples(const int32_t* m_dev, int64_t n_pairs, int budget, uint32_t seed, int32_t* samp_dev, void* stream);
+int sfm_verify_models(const int32_t* samp_dev, const int32_t* surv_dev, const int32_t* m_dev, const int32_t* pair_img_dev,
+                      const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes, int64_t n_pairs, int64_t cap, int budget,
+                      int32_t* nmodels_dev, double* E_dev, void* stream);
+int sfm_verify_score(const double* E_dev, const int32_t* nmodels_dev, const int32_t* surv_dev, const int32_t* m_dev,
+                     const int32_t* pair_img_dev, const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes,
+                     int64_t n_pairs, int64_t cap, int budget, float thr2, int32_t* counts_dev, uint64_t* best_dev, void* stream);
+int sfm_verify_select(const double* E_dev, const int32_t* nmodels_dev, const uint64_t* best_dev, const int32_t* surv_dev, const int32_t* m_dev,
+                      const int32_t* pair_img_dev, const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes,
+                      int64_t n_pairs, int64_t cap, int budget, float thr2, uint8_t* keep_dev, double* E_out_dev, double* Rt_dev,
+                      int32_t* info_dev, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

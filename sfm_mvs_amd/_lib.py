@@ -138,6 +138,12 @@ SIGNATURES = {
     "sfm_track_view_scores": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _i64, _f64, _f64, _int, _vp, _vp, _vp, _vp]),
     "sfm_track_correspondences_ws_bytes": (_sz, [_i64]),
     "sfm_track_correspondences": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_verify_normalise": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "sfm_verify_survivors": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _int, _f64, _vp, _vp, _vp]),
+    "sfm_verify_samples": (_int, [_vp, _i64, _int, _c.c_uint32, _vp, _vp]),
+    "sfm_verify_models": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "sfm_verify_score": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp]),
+    "sfm_verify_select": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

@@ -364,11 +364,22 @@ def densify_tracks(result, images, K, P, points=None, nsrc=4, min_angle_deg=None
     return out
 
 
-def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70):
+def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70, batched=False, **kw):
     """The per-query inlier masks of `sharded.HipVerifyEngine`'s two stages (isfm.py:73-94: essential-matrix RANSAC on the Lowe
     survivors, then the cheirality vote of recoverPose on its inliers) as the `keep` tensor of `match_edges`: uint8 [n_pairs, cap],
     1 at the queries that survive both.  A pair with fewer than five survivors or without an essential matrix keeps nothing.
-    Waits for the host as the engine does (per pair)."""
+    Waits for the host as the engine does (per pair).
+    batched=True: `verify.verify_pairs(...)["keep"]` instead (docs/tracks.md §11): all pairs in a fixed number of launches and no host wait, a fixed
+    budget of hypotheses per pair; **kw (threshold, budget, seed) goes to it.  The masks of the two paths differ."""
+    if batched:
+        from . import verify
+        dev = store.device
+        to_dev = lambda v, shape: (v.to(device=dev, dtype=torch.int32) if isinstance(v, torch.Tensor) else _upload(np.asarray(v, np.int32), dev)).reshape(shape).contiguous()
+        sizes = [int(k.shape[0]) for k in keypoints]
+        kp = torch.cat([k.to(device=dev, dtype=torch.float32).reshape(-1, 2) for k in keypoints]).contiguous()
+        return verify.verify_pairs(store.contiguous(), to_dev(n_query, (-1,)), to_dev(pairs, (-1, 2)), image_offsets(sizes, dev), kp, K, ratio, **kw)["keep"]
+    if kw:
+        raise TypeError(f"verify_keep: {sorted(kw)} apply to batched=True only")
     from . import ops, ransac
     dev = store.device
     n_pairs, cap = int(store.shape[0]), int(store.shape[2])

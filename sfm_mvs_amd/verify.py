@@ -1,0 +1,268 @@
+"""Geometric verification of all matched pairs at once (include/sfm_hip.h, "VERIFY"; docs/tracks.md §11).
+
+`normalise_keypoints`, `survivors`, `samples`, `models`, `score` and `select` are the six launches; each takes and returns device
+tensors and never waits for the host.  `verify_pairs` composes them and returns the `keep` mask `tracks.match_edges` takes, with every
+pair's essential matrix, relative pose and eight words of bookkeeping; the last three launches run once per chunk of pairs, so the
+models buffer is bounded (`MAX_MODELS_BYTES`).  A fixed budget of five-point hypotheses per pair, drawn by a
+counter-based sampler, replaces the sequential RANSAC of `ransac.find_essential_mat`: the result is a function of the inputs and the
+seed alone, and differs from the per-pair path's masks."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import SfmHipError, check, on_device, ptr, require_cuda, stream_ptr
+
+MAX_BUDGET = 1024
+# docs/tracks.md §11.4: the rule "the smallest budget past which neither the recall of planted inliers nor the share of planted outliers
+# kept improves by more than a point at 30 % inliers" does not settle inside the admitted range (the recall still rises by 4 to 13 points
+# from 512 to 1 024), so the default is the cap.
+DEFAULT_BUDGET = 1024
+DEFAULT_THRESHOLD = 0.4          # pixels, as HipVerifyEngine passes it to find_essential_mat
+DEFAULT_SEED = 0
+MAX_MODELS_BYTES = 256 << 20     # the models buffer of `verify_pairs`: 364 pairs a chunk at the default budget
+SLOTS = 10                       # models per sample
+FEW_SURVIVORS, NO_MODEL, NO_VOTE = 1, 2, 4
+
+
+def _i32(t, what, shape):
+    require_cuda(t)
+    if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise SfmHipError(f"verify: {what} must be a contiguous int32 device tensor of shape {tuple(shape)}")
+    return t
+
+
+def _typed(t, dtype, shape, what):
+    require_cuda(t)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise SfmHipError(f"verify: {what} must be a contiguous {dtype} device tensor of shape {tuple(shape)}")
+    return t
+
+
+def _K9(K):
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    return K
+
+
+def thr2_of(K, threshold=DEFAULT_THRESHOLD):
+    """(float)(thr * thr) with thr = threshold / ((K[0] + K[4]) / 2), as sfm_find_essential_mat computes it."""
+    K = _K9(K)
+    thr = float(threshold) / ((K[0] + K[4]) / 2)
+    return float(np.float32(thr * thr))
+
+
+def _budget(budget):
+    budget = int(budget)
+    if not 1 <= budget <= MAX_BUDGET:
+        raise SfmHipError(f"verify: the budget must be 1..{MAX_BUDGET} (got {budget})")
+    return budget
+
+
+def _n_img(img_off):
+    require_cuda(img_off)
+    if img_off.dtype != torch.int32 or img_off.dim() != 1 or img_off.numel() < 2 or not img_off.is_contiguous():
+        raise SfmHipError("verify: img_off must be a contiguous int32 [n_img + 1] device tensor with n_img >= 1")
+    return int(img_off.numel()) - 1
+
+
+def _xn(xn):
+    require_cuda(xn)
+    if xn.dtype != torch.float64 or xn.dim() != 2 or xn.shape[1] != 2 or not xn.is_contiguous():
+        raise SfmHipError("verify: xn must be a contiguous float64 [n_nodes, 2] device tensor")
+    return int(xn.shape[0])
+
+
+def _surv(surv):
+    require_cuda(surv)
+    if surv.dtype != torch.int32 or surv.dim() != 3 or surv.shape[2] != 2 or not surv.is_contiguous():
+        raise SfmHipError("verify: surv must be a contiguous int32 [n_pairs, cap, 2] device tensor")
+    return int(surv.shape[0]), int(surv.shape[1])
+
+
+def normalise_keypoints(kp, K, out=None):
+    """sfm_verify_normalise: kp float32 [n_nodes, 2] (all images concatenated) -> float64 [n_nodes, 2] K-normalised.  No host wait."""
+    require_cuda(kp)
+    if kp.dtype != torch.float32 or kp.dim() != 2 or kp.shape[1] != 2 or not kp.is_contiguous():
+        raise SfmHipError("normalise_keypoints: kp must be a contiguous float32 [n_nodes, 2] device tensor")
+    n = int(kp.shape[0])
+    K = _K9(K)
+    xn = torch.empty((n, 2), dtype=torch.float64, device=kp.device) if out is None else _typed(out, torch.float64, (n, 2), "xn")
+    with on_device(kp.device):
+        check(_lib.lib().sfm_verify_normalise(ptr(kp) if n else None, n, K.ctypes.data_as(ctypes.c_void_p), ptr(xn) if n else None, stream_ptr()),
+              "sfm_verify_normalise")
+    return xn
+
+
+def survivors(store, n_query, pairs, img_off, ratio=0.70, out=None):
+    """sfm_verify_survivors: the Lowe survivors of every pair of store (int32 [n_pairs, 2, cap, 2]) in ascending query order.
+    Returns (surv int32 [n_pairs, cap, 2] = (q, t) then (-1, -1), m int32 [n_pairs]).  No host wait."""
+    require_cuda(store)
+    if store.dtype != torch.int32 or store.dim() != 4 or store.shape[1] != 2 or store.shape[3] != 2 or not store.is_contiguous():
+        raise SfmHipError("survivors: store must be a contiguous int32 [n_pairs, 2, cap, 2] device tensor")
+    n_pairs, cap, dev = int(store.shape[0]), int(store.shape[2]), store.device
+    n_img = _n_img(img_off)
+    _i32(n_query, "n_query", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    if out is None:
+        out = (torch.empty((n_pairs, cap, 2), dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.int32, device=dev))
+    surv, m = _i32(out[0], "surv", (n_pairs, cap, 2)), _i32(out[1], "m", (n_pairs,))
+    ne = n_pairs * cap
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_survivors(ptr(store) if ne else None, n_pairs, cap, ptr(pairs) if n_pairs else None,
+                                              ptr(n_query) if n_pairs else None, ptr(img_off), n_img, float(ratio), ptr(surv) if ne else None,
+                                              ptr(m) if n_pairs else None, stream_ptr()), "sfm_verify_survivors")
+    return surv, m
+
+
+def samples(m, budget=DEFAULT_BUDGET, seed=DEFAULT_SEED, out=None):
+    """sfm_verify_samples: int32 [n_pairs, budget, 5] survivor indices, five times -1 where a sample could not be drawn.  No host wait."""
+    require_cuda(m)
+    if m.dtype != torch.int32 or m.dim() != 1 or not m.is_contiguous():
+        raise SfmHipError("samples: m must be a contiguous int32 [n_pairs] device tensor")
+    n_pairs, H = int(m.numel()), _budget(budget)
+    samp = torch.empty((n_pairs, H, 5), dtype=torch.int32, device=m.device) if out is None else _i32(out, "samp", (n_pairs, H, 5))
+    with on_device(m.device):
+        check(_lib.lib().sfm_verify_samples(ptr(m) if n_pairs else None, n_pairs, H, int(seed) & 0xFFFFFFFF, ptr(samp) if n_pairs else None,
+                                            stream_ptr()), "sfm_verify_samples")
+    return samp
+
+
+def models(samp, surv, m, pairs, img_off, xn, out=None):
+    """sfm_verify_models: the five-point models of every sample, the bits `hostgeom.five_point` returns.
+    Returns (nmodels int32 [n_pairs, H], E float64 [n_pairs, H, 10, 9], zero past nmodels).  No host wait."""
+    n_pairs, cap = _surv(surv)
+    n_img, n_nodes = _n_img(img_off), _xn(xn)
+    require_cuda(samp)
+    if samp.dtype != torch.int32 or samp.dim() != 3 or samp.shape[0] != n_pairs or samp.shape[2] != 5 or not samp.is_contiguous():
+        raise SfmHipError("models: samp must be a contiguous int32 [n_pairs, H, 5] device tensor")
+    H, dev = _budget(samp.shape[1]), surv.device
+    _i32(m, "m", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    if out is None:
+        out = (torch.empty((n_pairs, H), dtype=torch.int32, device=dev), torch.empty((n_pairs, H, SLOTS, 9), dtype=torch.float64, device=dev))
+    nmodels, E = _i32(out[0], "nmodels", (n_pairs, H)), _typed(out[1], torch.float64, (n_pairs, H, SLOTS, 9), "E")
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_models(ptr(samp) if n_pairs else None, ptr(surv) if n_pairs * cap else None, ptr(m) if n_pairs else None,
+                                           ptr(pairs) if n_pairs else None, ptr(img_off), n_img, ptr(xn) if n_nodes else None, n_nodes, n_pairs,
+                                           cap, H, ptr(nmodels) if n_pairs else None, ptr(E) if n_pairs else None, stream_ptr()),
+              "sfm_verify_models")
+    return nmodels, E
+
+
+def _scored(who, E, nmodels, surv, m, pairs, img_off, xn):
+    n_pairs, cap = _surv(surv)
+    n_img, n_nodes = _n_img(img_off), _xn(xn)
+    require_cuda(E, nmodels)
+    if nmodels.dtype != torch.int32 or nmodels.dim() != 2 or nmodels.shape[0] != n_pairs or not nmodels.is_contiguous():
+        raise SfmHipError(f"{who}: nmodels must be a contiguous int32 [n_pairs, H] device tensor")
+    H = _budget(nmodels.shape[1])
+    _typed(E, torch.float64, (n_pairs, H, SLOTS, 9), "E")
+    _i32(m, "m", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    return n_pairs, cap, n_img, n_nodes, H
+
+
+def score(E, nmodels, surv, m, pairs, img_off, xn, thr2, out=None):
+    """sfm_verify_score: (counts int32 [n_pairs, H, 10], best int64 [n_pairs] holding the uint64 key
+    (count << 32) | (0xFFFFFFFF - (10 s + j)) of the best model, 0 without one).  thr2: `thr2_of(K, threshold)`.  No host wait."""
+    n_pairs, cap, n_img, n_nodes, H = _scored("score", E, nmodels, surv, m, pairs, img_off, xn)
+    dev = surv.device
+    if out is None:
+        out = (torch.empty((n_pairs, H, SLOTS), dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.int64, device=dev))
+    counts, best = _i32(out[0], "counts", (n_pairs, H, SLOTS)), _typed(out[1], torch.int64, (n_pairs,), "best")
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_score(ptr(E) if n_pairs else None, ptr(nmodels) if n_pairs else None, ptr(surv) if n_pairs * cap else None,
+                                          ptr(m) if n_pairs else None, ptr(pairs) if n_pairs else None, ptr(img_off), n_img,
+                                          ptr(xn) if n_nodes else None, n_nodes, n_pairs, cap, H, float(thr2), ptr(counts) if n_pairs else None,
+                                          ptr(best) if n_pairs else None, stream_ptr()), "sfm_verify_score")
+    return counts, best
+
+
+def select(E, nmodels, best, surv, m, pairs, img_off, xn, thr2, out=None):
+    """sfm_verify_select: (keep uint8 [n_pairs, cap], E float64 [n_pairs, 9], Rt float64 [n_pairs, 12], info int32 [n_pairs, 8]) of the
+    best model of every pair.  No host wait."""
+    n_pairs, cap, n_img, n_nodes, H = _scored("select", E, nmodels, surv, m, pairs, img_off, xn)
+    dev = surv.device
+    _typed(best, torch.int64, (n_pairs,), "best")
+    if out is None:
+        out = (torch.empty((n_pairs, cap), dtype=torch.uint8, device=dev), torch.empty((n_pairs, 9), dtype=torch.float64, device=dev),
+               torch.empty((n_pairs, 12), dtype=torch.float64, device=dev), torch.empty((n_pairs, 8), dtype=torch.int32, device=dev))
+    keep, Eb, Rt, info = out
+    _typed(keep, torch.uint8, (n_pairs, cap), "keep")
+    _typed(Eb, torch.float64, (n_pairs, 9), "E_out")
+    _typed(Rt, torch.float64, (n_pairs, 12), "Rt")
+    _i32(info, "info", (n_pairs, 8))
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_select(ptr(E) if n_pairs else None, ptr(nmodels) if n_pairs else None, ptr(best) if n_pairs else None,
+                                           ptr(surv) if n_pairs * cap else None, ptr(m) if n_pairs else None, ptr(pairs) if n_pairs else None,
+                                           ptr(img_off), n_img, ptr(xn) if n_nodes else None, n_nodes, n_pairs, cap, H, float(thr2),
+                                           ptr(keep) if n_pairs * cap else None, ptr(Eb) if n_pairs else None, ptr(Rt) if n_pairs else None,
+                                           ptr(info) if n_pairs else None, stream_ptr()), "sfm_verify_select")
+    return keep, Eb, Rt, info
+
+
+def pairs_per_chunk(budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES):
+    """How many pairs `verify_pairs` solves, scores and selects at a time: the models of a chunk (720 bytes a sample) fit `max_models_bytes`."""
+    return max(1, int(max_models_bytes) // (_budget(budget) * SLOTS * 72))
+
+
+def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DEFAULT_THRESHOLD, budget=DEFAULT_BUDGET, seed=DEFAULT_SEED,
+                 max_models_bytes=MAX_MODELS_BYTES):
+    """All pairs in a fixed number of launches and no host wait.  store int32 [n_pairs, 2, cap, 2], n_query int32 [n_pairs], pairs int32
+    [n_pairs, 2], img_off int32 [n_img + 1], kp float32 [n_nodes, 2]: device tensors, as `tracks.match_edges` takes them; K: 3 x 3 on the
+    host.  Keypoints, survivors and samples are computed for all pairs at once (three launches); models, scores and the selection run over
+    chunks of `pairs_per_chunk(budget, max_models_bytes)` pairs (three launches and two clears a chunk) that share one models buffer, so the
+    workspace does not grow with the number of pairs beyond the survivors and samples.  A sample is a function of (seed, pair, sample), so
+    the chunking does not change a word of the result.
+    Returns a dict of device tensors: keep uint8 [n_pairs, cap] (what `match_edges(keep=...)` takes), E float64 [n_pairs, 9],
+    Rt float64 [n_pairs, 12] (the relative pose [R | t], 3 x 4 row-major, |t| = 1), info int32 [n_pairs, 8] (survivors, models scored,
+    Sampson inliers, cheirality inliers, best sample, best model, winning candidate, status bits)."""
+    thr2 = thr2_of(K, threshold)
+    xn = normalise_keypoints(kp, K)
+    surv, m = survivors(store, n_query, pairs, img_off, ratio)
+    samp = samples(m, budget, seed)
+    n_pairs, cap, H, dev = int(surv.shape[0]), int(surv.shape[1]), int(samp.shape[1]), surv.device
+    keep = torch.empty((n_pairs, cap), dtype=torch.uint8, device=dev)
+    Eb = torch.empty((n_pairs, 9), dtype=torch.float64, device=dev)
+    Rt = torch.empty((n_pairs, 12), dtype=torch.float64, device=dev)
+    info = torch.empty((n_pairs, 8), dtype=torch.int32, device=dev)
+    step = min(pairs_per_chunk(H, max_models_bytes), max(n_pairs, 1))
+    nmodels = torch.empty((step, H), dtype=torch.int32, device=dev)
+    E = torch.empty((step, H, SLOTS, 9), dtype=torch.float64, device=dev)
+    counts = torch.empty((step, H, SLOTS), dtype=torch.int32, device=dev)
+    best = torch.empty(step, dtype=torch.int64, device=dev)
+    for a in range(0, n_pairs, step):
+        b = min(a + step, n_pairs)
+        k = b - a
+        part = (surv[a:b], m[a:b], pairs[a:b], img_off, xn)
+        models(samp[a:b], *part, out=(nmodels[:k], E[:k]))
+        score(E[:k], nmodels[:k], *part, thr2, out=(counts[:k], best[:k]))
+        select(E[:k], nmodels[:k], best[:k], *part, thr2, out=(keep[a:b], Eb[a:b], Rt[a:b], info[a:b]))
+    return dict(keep=keep, E=Eb, Rt=Rt, info=info)
+
+
+def workspace_bytes(n_pairs, cap, budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES):
+    """Bytes of the intermediate tensors `verify_pairs` allocates, without xn: survivors and samples of all pairs, and the models, model
+    counts, inlier counts and best keys of one chunk."""
+    n_pairs, cap, H = int(n_pairs), int(cap), int(budget)
+    step = min(pairs_per_chunk(H, max_models_bytes), max(n_pairs, 1))
+    return n_pairs * (cap * 8 + 4 + H * 20) + step * (H * (4 + SLOTS * 72 + SLOTS * 4) + 8)
+
+
+def confidence_iters(info, prob=0.999):
+    """The iteration bound of sequential RANSAC (`ransac_update_num_iters`: log(1 - prob) / log(1 - w^5)) at the inlier ratio w each
+    pair achieved (Sampson inliers / survivors): a pair whose bound exceeds the budget was not covered with confidence `prob`.
+    info: the int32 [n_pairs, 8] of `verify_pairs` (a device tensor is downloaded: a host wait).  Returns float64 [n_pairs]; inf where
+    no model was found, 0 where every survivor is an inlier."""
+    info = info.cpu().numpy() if isinstance(info, torch.Tensor) else np.asarray(info)
+    m, inl = info[:, 0].astype(np.float64), info[:, 2].astype(np.float64)
+    w = np.divide(inl, m, out=np.zeros_like(m), where=m > 0)
+    out = np.full(len(m), np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        denom = 1.0 - w ** 5
+        num = np.log(max(1.0 - float(prob), np.finfo(np.float64).tiny))
+        ok = (w > 0) & (denom >= np.finfo(np.float64).tiny)
+        out[ok] = np.rint(num / np.log(denom[ok]))
+        out[(w > 0) & ~ok] = 0.0
+    return out
