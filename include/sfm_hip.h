@@ -1380,6 +1380,65 @@ int sfm_verify_select(const double* E_dev, const int32_t* nmodels_dev, const uin
                       int64_t n_pairs, int64_t cap, int budget, float thr2, uint8_t* keep_dev, double* E_out_dev, double* Rt_dev,
                       int32_t* info_dev, void* stream);
 
+/* ------------------------------------------------------------------------
+ * VERIFY-LO (csrc/verify_lo.hip, docs/tracks.md section 12): local optimisation of VERIFY's best hypotheses.  Between sfm_verify_score
+ * and sfm_verify_select: the T best models of a pair are each refitted R times on their inliers under a widened threshold by the
+ * eight-point system, recounted at thr2, and the best of all is handed to the UNCHANGED sfm_verify_select as a one-sample models buffer
+ * (budget = 1).  Three launches, on the caller's stream, no host wait.  Arithmetic as VERIFY: float64, correctly rounded, in the order
+ * written, no FMA, only + - * / sqrt fabs and comparisons; every integer output is a count, a maximum of a key or a copy.
+ * tests/np_verify_lo.py restates every output word.  E, nmodels, counts, surv, m, pair_img, img_off, xn, thr2, m', "slot": as VERIFY.
+ *
+ * sfm_verify_top — the key of model (s, j), j < nmodels[p][s] (clamped to 0..10), is ((uint32)counts[p][s][j] << 32) |
+ *   (0xFFFFFFFF - (10 s + j)).  top_dev uint64 [n_pairs][T], T = top in 1..16: the T largest keys of the pair in descending order,
+ *   then zeros.  Keys are distinct; top[p][0] is sfm_verify_score's best[p].
+ *
+ * sfm_verify_lo — candidate (p, t) has a model when top[p][t] != 0 and its slot is < 10 H; without one E_lo = 0, n_lo = 0,
+ *   round_lo = -1.  Otherwise, with v(E, e) the float value sfm_verify_score compares with thr2 for survivor e (over the same survivors:
+ *   the first m' whose two nodes lie in 0..n_nodes-1) and n(E) the number of survivors with v <= thr2:
+ *     E_cur = the model of the slot;  E_best = E_cur;  n_best = n(E_cur);  round_lo = -1
+ *     for r = 0 .. R-1  (R = rounds in 0..8, wide2[r] = wide2_host[r], a float that is not NaN):
+ *       W = the survivors with v(E_cur, e) <= wide2[r];  fewer than 8: stop
+ *       per survivor a = (a2 a1, a2 b1, a2, b2 a1, b2 b1, b2, a1, b1, 1);  M[i][j] = M[j][i] = the sum over W of a[i] * a[j], i <= j,
+ *         in this order: s_l (l = 0..255) starts at 0 and takes, for e = l, l + 256, l + 512, .. < m' in ascending order, s_l = s_l +
+ *         a[i] * a[j] when e is in W;  then for h = 1, 2, 4, .. 128:  s_l = s_l + s_(l + h) for every l that is a multiple of 2 h;
+ *         M[i][j] = s_0
+ *       E_new = refit(M) (below);  a non-finite word in E_new: stop
+ *       n_new = n(E_new);  when n_new > n_best:  E_best = E_new, n_best = n_new, round_lo = r
+ *       E_cur = E_new
+ *   (n(E_new) and the sums of the next round are formed in one pass over the survivors: R + 1 passes.)
+ *   E_lo_dev float64 [n_pairs][T][9] = E_best;  n_lo_dev int32 [n_pairs][T] = n_best;  round_lo_dev int32 [n_pairs][T].
+ *   n_lo of candidate 0 is never below the count of sfm_verify_score's best model: round -1 is that model itself.
+ *
+ * refit(M) = sfm_host_verify_refit(M81_host, E_host), the function the kernel's lane 0 runs, compiled for the host:
+ *   cv::SVD's one-sided Jacobi (csrc/host_solvers.h, Svd: JacobiSVDImpl_, eps = 10 DBL_EPSILON, at most 30 sweeps, the singular values
+ *   sorted descending by its selection sort) on the rows a_i[k] = M[k][i] of the 9 x 9 matrix; F (3 x 3 row-major) = the right
+ *   singular vector of the smallest singular value (row 8 of vt; u is not formed).  (U, Vt) = cv::SVD of F (Svd::compute, 3 x 3).
+ *   e[i][j] = U[i][0] * Vt[0][j] + U[i][1] * Vt[1][j];  nrm = sqrt(the sum of e[i][j] * e[i][j], row-major from 0);  E = e / nrm.
+ *
+ * sfm_verify_lo_pick — per pair, over the candidates t that have a model, the largest ((uint32)n_lo[p][t] << 32) | (0xFFFFFFFF - t):
+ *   the most inliers, the lowest t on ties.  It writes what sfm_verify_select takes at budget = 1:
+ *   E_sel_dev float64 [n_pairs][1][10][9]: the winner's E_lo in slot 0, zeros elsewhere;  nmodels_sel_dev int32 [n_pairs][1]: 1, or 0
+ *   when no candidate has a model;  best_sel_dev uint64 [n_pairs]: (n_lo << 32) | 0xFFFFFFFF, or 0.
+ *   lo_info_dev int32 [n_pairs][8]: top[p][0] >> 32 (the plain best count), the winner's n_lo, the winner t, its round_lo, its origin
+ *   sample slot / 10 and origin model slot % 10 (the slot of top[p][t]), the number of candidates that have a model, 0.  Without a
+ *   winner: (top[p][0] >> 32, 0, -1, -1, -1, -1, 0, 0).
+ *
+ * Errors (SFM_ERR_ARG, before any device call): n_pairs negative or above (2^31 - 1) / 10 240, budget outside 1..1024, top outside
+ *   1..16, rounds outside 0..8, a NaN in wide2_host, negative sizes, n_pairs * cap or n_nodes above 2^31 - 1, n_img outside 1..65 536,
+ *   NULL where the count is non-zero (img_off_dev always; wide2_host when rounds > 0).
+ * ---------------------------------------------------------------------- */
+#define SFM_VERIFY_LO_MAX_TOP 16
+#define SFM_VERIFY_LO_MAX_ROUNDS 8
+int sfm_verify_top(const int32_t* counts_dev, const int32_t* nmodels_dev, int64_t n_pairs, int budget, int top, uint64_t* top_dev, void* stream);
+int sfm_verify_lo(const double* E_dev, const uint64_t* top_dev, int top, const int32_t* surv_dev, const int32_t* m_dev,
+                  const int32_t* pair_img_dev, const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes, int64_t n_pairs,
+                  int64_t cap, int budget, float thr2, int rounds, const float* wide2_host, double* E_lo_dev, int32_t* n_lo_dev,
+                  int32_t* round_lo_dev, void* stream);
+int sfm_verify_lo_pick(const uint64_t* top_dev, const double* E_lo_dev, const int32_t* n_lo_dev, const int32_t* round_lo_dev, int64_t n_pairs,
+                       int budget, int top, double* E_sel_dev, int32_t* nmodels_sel_dev, uint64_t* best_sel_dev, int32_t* lo_info_dev,
+                       void* stream);
+int sfm_host_verify_refit(const double* M81_host, double* E_host);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

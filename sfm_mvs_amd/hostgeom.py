@@ -48,6 +48,15 @@ def decompose_essential(E):
     return R1, R2, t
 
 
+def verify_refit(M):
+    """The refit of the local optimisation (`sfm_host_verify_refit`): the 9 x 9 moment matrix of the eight-point system -> the essential
+    matrix of its smallest singular vector (3, 3), unit Frobenius norm.  The function lane 0 of `sfm_verify_lo` runs, on the host."""
+    Mc = np.ascontiguousarray(np.asarray(M, np.float64).reshape(81))
+    E = np.empty(9)
+    _lib.check(_lib.lib().sfm_host_verify_refit(Mc.ctypes.data_as(_vp), E.ctypes.data_as(_vp)), "sfm_host_verify_refit")
+    return E.reshape(3, 3)
+
+
 def epnp(K, Xw, uv):
     """EPnP on 4..64 correspondences (`sfm_host_epnp`): R (3,3), t (3,)."""
     Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))

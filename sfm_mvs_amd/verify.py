@@ -5,7 +5,10 @@ tensors and never waits for the host.  `verify_pairs` composes them and returns 
 pair's essential matrix, relative pose and eight words of bookkeeping; the last three launches run once per chunk of pairs, so the
 models buffer is bounded (`MAX_MODELS_BYTES`).  A fixed budget of five-point hypotheses per pair, drawn by a
 counter-based sampler, replaces the sequential RANSAC of `ransac.find_essential_mat`: the result is a function of the inputs and the
-seed alone, and differs from the per-pair path's masks."""
+seed alone, and differs from the per-pair path's masks.
+
+`top_models`, `local_optimise` and `pick` are the three launches of the local optimisation ("VERIFY-LO"; docs/tracks.md §12) that
+`verify_pairs(lo=...)` puts between `score` and `select`: the best models of a pair refitted on their inliers and recounted."""
 import ctypes
 
 import numpy as np
@@ -24,6 +27,10 @@ DEFAULT_SEED = 0
 MAX_MODELS_BYTES = 256 << 20     # the models buffer of `verify_pairs`: 364 pairs a chunk at the default budget
 SLOTS = 10                       # models per sample
 FEW_SURVIVORS, NO_MODEL, NO_VOTE = 1, 2, 4
+MAX_TOP, MAX_ROUNDS = 16, 8      # SFM_VERIFY_LO_MAX_TOP, SFM_VERIFY_LO_MAX_ROUNDS
+# docs/tracks.md §12.4: the setting with the smallest top * rounds whose mean recall over the nine 30 % scenes is within a point of the
+# best setting tried and whose share of planted outliers kept stays within a point of the plain path's on every (share, m) mean.
+DEFAULT_LO = dict(top=1, rounds=1, widen=(3.0,))
 
 
 def _i32(t, what, shape):
@@ -202,13 +209,117 @@ def select(E, nmodels, best, surv, m, pairs, img_off, xn, thr2, out=None):
     return keep, Eb, Rt, info
 
 
+def _top(top):
+    top = int(top)
+    if not 1 <= top <= MAX_TOP:
+        raise SfmHipError(f"verify: top must be 1..{MAX_TOP} (got {top})")
+    return top
+
+
+def top_models(counts, nmodels, top, out=None):
+    """sfm_verify_top: int64 [n_pairs, top] holding the uint64 keys of the `top` best models of every pair in descending order, then
+    zeros; column 0 is `score`'s best.  counts int32 [n_pairs, H, 10], nmodels int32 [n_pairs, H].  No host wait."""
+    require_cuda(counts, nmodels)
+    if nmodels.dtype != torch.int32 or nmodels.dim() != 2 or not nmodels.is_contiguous():
+        raise SfmHipError("top_models: nmodels must be a contiguous int32 [n_pairs, H] device tensor")
+    n_pairs, H, T = int(nmodels.shape[0]), _budget(nmodels.shape[1]), _top(top)
+    _i32(counts, "counts", (n_pairs, H, SLOTS))
+    keys = torch.empty((n_pairs, T), dtype=torch.int64, device=nmodels.device) if out is None else _typed(out, torch.int64, (n_pairs, T), "top")
+    with on_device(nmodels.device):
+        check(_lib.lib().sfm_verify_top(ptr(counts) if n_pairs else None, ptr(nmodels) if n_pairs else None, n_pairs, H, T,
+                                        ptr(keys) if n_pairs else None, stream_ptr()), "sfm_verify_top")
+    return keys
+
+
+def _wide2(wide2):
+    w = np.ascontiguousarray(np.asarray(wide2, np.float32).reshape(-1))
+    if len(w) > MAX_ROUNDS or np.isnan(w).any():
+        raise SfmHipError(f"verify: wide2 must hold 0..{MAX_ROUNDS} squared thresholds, none a NaN (got {w.tolist()})")
+    return w
+
+
+def local_optimise(E, top, surv, m, pairs, img_off, xn, thr2, wide2, out=None):
+    """sfm_verify_lo: every candidate of `top` (int64 [n_pairs, T], as `top_models` leaves it) refitted len(wide2) times on its inliers
+    under the squared thresholds wide2 (floats on the host, `thr2_of(K, widen * threshold)`) and recounted at thr2.
+    Returns (E_lo float64 [n_pairs, T, 9], n_lo int32 [n_pairs, T], round_lo int32 [n_pairs, T]): the best of each candidate and its
+    refits, its inlier count, and the round that produced it (-1: the candidate itself).  No host wait."""
+    n_pairs, cap = _surv(surv)
+    n_img, n_nodes = _n_img(img_off), _xn(xn)
+    require_cuda(E, top)
+    if E.dtype != torch.float64 or E.dim() != 4 or E.shape[0] != n_pairs or tuple(E.shape[2:]) != (SLOTS, 9) or not E.is_contiguous():
+        raise SfmHipError("local_optimise: E must be a contiguous float64 [n_pairs, H, 10, 9] device tensor")
+    H, dev = _budget(E.shape[1]), surv.device
+    if top.dtype != torch.int64 or top.dim() != 2 or top.shape[0] != n_pairs or not top.is_contiguous():
+        raise SfmHipError("local_optimise: top must be a contiguous int64 [n_pairs, T] device tensor")
+    T, w = _top(top.shape[1]), _wide2(wide2)
+    _i32(m, "m", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    if out is None:
+        out = (torch.empty((n_pairs, T, 9), dtype=torch.float64, device=dev), torch.empty((n_pairs, T), dtype=torch.int32, device=dev),
+               torch.empty((n_pairs, T), dtype=torch.int32, device=dev))
+    E_lo, n_lo, round_lo = _typed(out[0], torch.float64, (n_pairs, T, 9), "E_lo"), _i32(out[1], "n_lo", (n_pairs, T)), _i32(out[2], "round_lo", (n_pairs, T))
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_lo(ptr(E) if n_pairs else None, ptr(top) if n_pairs else None, T, ptr(surv) if n_pairs * cap else None,
+                                       ptr(m) if n_pairs else None, ptr(pairs) if n_pairs else None, ptr(img_off), n_img,
+                                       ptr(xn) if n_nodes else None, n_nodes, n_pairs, cap, H, float(thr2), len(w),
+                                       w.ctypes.data_as(ctypes.c_void_p) if len(w) else None, ptr(E_lo) if n_pairs else None,
+                                       ptr(n_lo) if n_pairs else None, ptr(round_lo) if n_pairs else None, stream_ptr()), "sfm_verify_lo")
+    return E_lo, n_lo, round_lo
+
+
+def pick(top, E_lo, n_lo, round_lo, budget, out=None):
+    """sfm_verify_lo_pick: the candidate with the most inliers of every pair (the lowest on ties), as the one-sample models buffer
+    `select` takes.  `budget`: the H of the models the keys of `top` index.  Returns (E_sel float64 [n_pairs, 1, 10, 9], nmodels_sel int32
+    [n_pairs, 1], best_sel int64 [n_pairs], lo_info int32 [n_pairs, 8] = plain best count, LO count, winning candidate, its round, its
+    origin sample and model, candidates that had a model, 0).  No host wait."""
+    require_cuda(top, E_lo, n_lo, round_lo)
+    if top.dtype != torch.int64 or top.dim() != 2 or not top.is_contiguous():
+        raise SfmHipError("pick: top must be a contiguous int64 [n_pairs, T] device tensor")
+    n_pairs, T, H, dev = int(top.shape[0]), _top(top.shape[1]), _budget(budget), top.device
+    _typed(E_lo, torch.float64, (n_pairs, T, 9), "E_lo")
+    _i32(n_lo, "n_lo", (n_pairs, T))
+    _i32(round_lo, "round_lo", (n_pairs, T))
+    if out is None:
+        out = (torch.empty((n_pairs, 1, SLOTS, 9), dtype=torch.float64, device=dev), torch.empty((n_pairs, 1), dtype=torch.int32, device=dev),
+               torch.empty(n_pairs, dtype=torch.int64, device=dev), torch.empty((n_pairs, 8), dtype=torch.int32, device=dev))
+    E_sel, nm_sel, best_sel, lo_info = out
+    _typed(E_sel, torch.float64, (n_pairs, 1, SLOTS, 9), "E_sel")
+    _i32(nm_sel, "nmodels_sel", (n_pairs, 1))
+    _typed(best_sel, torch.int64, (n_pairs,), "best_sel")
+    _i32(lo_info, "lo_info", (n_pairs, 8))
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_lo_pick(*(ptr(t) if n_pairs else None for t in (top, E_lo, n_lo, round_lo)), n_pairs, H, T,
+                                            *(ptr(t) if n_pairs else None for t in (E_sel, nm_sel, best_sel, lo_info)), stream_ptr()),
+              "sfm_verify_lo_pick")
+    return E_sel, nm_sel, best_sel, lo_info
+
+
+def lo_settings(lo):
+    """`lo=True` or dict(top=, rounds=, widen=) -> (top, widen tuple of `rounds` multipliers of the threshold); None for lo=None."""
+    if lo is None or lo is False:
+        return None
+    if lo is True:
+        lo = {}
+    if not isinstance(lo, dict) or set(lo) - {"top", "rounds", "widen"}:
+        raise SfmHipError(f"verify: lo must be None, True or a dict of top, rounds, widen (got {lo!r})")
+    top = _top(lo.get("top", DEFAULT_LO["top"]))
+    widen = lo.get("widen")
+    if widen is None:                                               # the default's multiplier in every round
+        widen = (DEFAULT_LO["widen"][0],) * int(lo.get("rounds", DEFAULT_LO["rounds"]))
+    widen = tuple(float(w) for w in widen)
+    rounds = lo.get("rounds", len(widen))
+    if not 0 <= int(rounds) <= MAX_ROUNDS or len(widen) != int(rounds) or any(not w > 0 for w in widen):
+        raise SfmHipError(f"verify: lo needs rounds in 0..{MAX_ROUNDS} and as many positive multipliers in widen (got rounds {rounds}, widen {widen})")
+    return top, widen
+
+
 def pairs_per_chunk(budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES):
     """How many pairs `verify_pairs` solves, scores and selects at a time: the models of a chunk (720 bytes a sample) fit `max_models_bytes`."""
     return max(1, int(max_models_bytes) // (_budget(budget) * SLOTS * 72))
 
 
 def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DEFAULT_THRESHOLD, budget=DEFAULT_BUDGET, seed=DEFAULT_SEED,
-                 max_models_bytes=MAX_MODELS_BYTES):
+                 max_models_bytes=MAX_MODELS_BYTES, lo=None):
     """All pairs in a fixed number of launches and no host wait.  store int32 [n_pairs, 2, cap, 2], n_query int32 [n_pairs], pairs int32
     [n_pairs, 2], img_off int32 [n_img + 1], kp float32 [n_nodes, 2]: device tensors, as `tracks.match_edges` takes them; K: 3 x 3 on the
     host.  Keypoints, survivors and samples are computed for all pairs at once (three launches); models, scores and the selection run over
@@ -217,7 +328,13 @@ def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DE
     the chunking does not change a word of the result.
     Returns a dict of device tensors: keep uint8 [n_pairs, cap] (what `match_edges(keep=...)` takes), E float64 [n_pairs, 9],
     Rt float64 [n_pairs, 12] (the relative pose [R | t], 3 x 4 row-major, |t| = 1), info int32 [n_pairs, 8] (survivors, models scored,
-    Sampson inliers, cheirality inliers, best sample, best model, winning candidate, status bits)."""
+    Sampson inliers, cheirality inliers, best sample, best model, winning candidate, status bits).
+    lo: None (the plain path, launch for launch), True (`DEFAULT_LO`) or dict(top=, rounds=, widen=): local optimisation (docs/tracks.md
+    §12) of the `top` best models of every pair, `rounds` refits each on the inliers under widen[r] * threshold; three more launches a
+    chunk between `score` and `select`, which then runs on the winner alone.  The Sampson inliers of a pair (info[:, 2]) are never fewer
+    than without; best sample and best model name the five-point model the winner was refitted from; the dict gains lo_info int32
+    [n_pairs, 8] (plain best count, LO count, winning candidate, its round or -1, origin sample, origin model, candidates, 0)."""
+    settings = lo_settings(lo)
     thr2 = thr2_of(K, threshold)
     xn = normalise_keypoints(kp, K)
     surv, m = survivors(store, n_query, pairs, img_off, ratio)
@@ -232,22 +349,48 @@ def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DE
     E = torch.empty((step, H, SLOTS, 9), dtype=torch.float64, device=dev)
     counts = torch.empty((step, H, SLOTS), dtype=torch.int32, device=dev)
     best = torch.empty(step, dtype=torch.int64, device=dev)
+    if settings is not None:
+        T, widen = settings
+        wide2 = [thr2_of(K, w * float(threshold)) for w in widen]
+        lo_info = torch.empty((n_pairs, 8), dtype=torch.int32, device=dev)
+        top = torch.empty((step, T), dtype=torch.int64, device=dev)
+        cand = (torch.empty((step, T, 9), dtype=torch.float64, device=dev), torch.empty((step, T), dtype=torch.int32, device=dev),
+                torch.empty((step, T), dtype=torch.int32, device=dev))
+        E_sel = torch.empty((step, 1, SLOTS, 9), dtype=torch.float64, device=dev)
+        nm_sel = torch.empty((step, 1), dtype=torch.int32, device=dev)
+        best_sel = torch.empty(step, dtype=torch.int64, device=dev)
     for a in range(0, n_pairs, step):
         b = min(a + step, n_pairs)
         k = b - a
         part = (surv[a:b], m[a:b], pairs[a:b], img_off, xn)
         models(samp[a:b], *part, out=(nmodels[:k], E[:k]))
         score(E[:k], nmodels[:k], *part, thr2, out=(counts[:k], best[:k]))
-        select(E[:k], nmodels[:k], best[:k], *part, thr2, out=(keep[a:b], Eb[a:b], Rt[a:b], info[a:b]))
-    return dict(keep=keep, E=Eb, Rt=Rt, info=info)
+        if settings is None:
+            select(E[:k], nmodels[:k], best[:k], *part, thr2, out=(keep[a:b], Eb[a:b], Rt[a:b], info[a:b]))
+            continue
+        top_models(counts[:k], nmodels[:k], T, out=top[:k])
+        local_optimise(E[:k], top[:k], *part, thr2, wide2, out=tuple(t[:k] for t in cand))
+        pick(top[:k], *(t[:k] for t in cand), H, out=(E_sel[:k], nm_sel[:k], best_sel[:k], lo_info[a:b]))
+        select(E_sel[:k], nm_sel[:k], best_sel[:k], *part, thr2, out=(keep[a:b], Eb[a:b], Rt[a:b], info[a:b]))
+        # `select` saw one sample of one model: models scored, best sample and best model keep their documented meaning
+        info[a:b, 1] = nmodels[:k].clamp(0, SLOTS).sum(1, dtype=torch.int32)
+        info[a:b, 4:6] = lo_info[a:b, 4:6]
+    if settings is None:
+        return dict(keep=keep, E=Eb, Rt=Rt, info=info)
+    return dict(keep=keep, E=Eb, Rt=Rt, info=info, lo_info=lo_info)
 
 
-def workspace_bytes(n_pairs, cap, budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES):
+def workspace_bytes(n_pairs, cap, budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES, lo=None):
     """Bytes of the intermediate tensors `verify_pairs` allocates, without xn: survivors and samples of all pairs, and the models, model
-    counts, inlier counts and best keys of one chunk."""
+    counts, inlier counts and best keys of one chunk; with `lo`, the keys, models, counts and rounds of a chunk's candidates and its
+    one-sample models buffer as well."""
     n_pairs, cap, H = int(n_pairs), int(cap), int(budget)
     step = min(pairs_per_chunk(H, max_models_bytes), max(n_pairs, 1))
-    return n_pairs * (cap * 8 + 4 + H * 20) + step * (H * (4 + SLOTS * 72 + SLOTS * 4) + 8)
+    total = n_pairs * (cap * 8 + 4 + H * 20) + step * (H * (4 + SLOTS * 72 + SLOTS * 4) + 8)
+    settings = lo_settings(lo)
+    if settings is not None:
+        total += step * (settings[0] * (8 + 72 + 4 + 4) + SLOTS * 72 + 4 + 8)
+    return total
 
 
 def confidence_iters(info, prob=0.999):
