@@ -661,7 +661,14 @@ constexpr int kMinfoPairMode = 0, kMinfoBatchMode = kMaxBatch, kMinfoTmax = 16, 
               kMinfoTicket = 51,  // knn_split_images_kernel's repair: arrival ticket — the workgroup that draws the LAST one reduces the rewritten words
                                   // (zeroed by the prep launch)
               kMinfoQ8S = 56, kMinfoQ8Lo = 64,   // per pair: the quantisation grid x ~ lo + s k, k = 0 .. 255 (float bits; written by the prep launch)
-              kMinfoWords = 72;   // written by knn_split_images_kernel (block 0); kMinfoI8: 1 = the exact-integer body runs, kMinfoBase: its per-pair score offset
+              // per pair, float bits: what refine_q8_body needs of the grid and the train residual, computed once by reduce_modes (not by
+              // each of the pair's refine waves): 1 / s, kQ8Eta / s, sqrt(the largest train residual) and the absolute term of the
+              // slack E, 24 * 2^-24 max(|lo|, |lo + 255 s|) (1 + 1e-6)
+              kMinfoQ8InvS = 72, kMinfoQ8EtaS = 80, kMinfoQ8TeRt = 88, kMinfoQ8Abs = 96,
+              kMinfoWords = 104;  // written by knn_split_images_kernel (block 0); kMinfoI8: 1 = the exact-integer body runs, kMinfoBase: its per-pair score offset
+static_assert(kMinfoQ8InvS == kMinfoQ8Lo + kMaxBatch && kMinfoWords == kMinfoQ8Abs + kMaxBatch, "one word per pair");
+// refine_q8_body's margins (explained there; up here because reduce_modes prices kQ8Eta in units of the pair's grid step)
+constexpr float kQ8Rho = 4e-6f, kQ8Eta = 1e-17f;
 __device__ __forceinline__ int knn_batch_mode(const int* __restrict__ flags, const float* __restrict__ bmax, int n_pairs, int lane) {
     int mode = kModeHalfExact;
     for (int b = 0; b < n_pairs; ++b) mode = max(mode, knn_filter_mode(flags + b * kNormBlocks, bmax + b * kNormBlocks, lane));
@@ -1342,6 +1349,17 @@ __global__ __launch_bounds__(kSplitThreads) void knn_split_images_kernel(BatchPt
                     s8base[wave] = base;
                     s8some[wave] = some ? 1 : 0;
                     sq8[wave] = q8p ? 1 : 0;
+                }
+                if (lane == 0 && leave) {
+                    // refine_q8_body's pair constants (u8 pairs of a quantised batch and pairs repaired below included), in the float32
+                    // association of its slack E (see there; tests/test_q8_bounds.py restates it): the certificate's bits depend on it
+                    const float lof = __int_as_float(minfo[kMinfoQ8Lo + wave]);
+                    const float inv_s = 1.f / s8;
+                    const float mabs = fmaxf(fabsf(lof), fabsf(lof + 255.f * s8));
+                    minfo[kMinfoQ8InvS + wave] = __float_as_int(inv_s);
+                    minfo[kMinfoQ8EtaS + wave] = __float_as_int(kQ8Eta * inv_s);
+                    minfo[kMinfoQ8TeRt + wave] = __float_as_int(sqrtf(te));
+                    minfo[kMinfoQ8Abs + wave] = __float_as_int(24.f * 5.9604645e-08f * mabs * (1.f + 1e-6f));
                 }
             }
             if (lane == 0) {
@@ -3102,7 +3120,7 @@ __device__ __forceinline__ void refine_i8_body(
 // u8 pairs inside a quantised batch are the case s = 1, lo = 0, E ~ 0.
 // Everything below is float32 arithmetic in units of s on numbers <= 2^23; kQ8Rho = 4e-6 carries rho (1.9e-6) AND the roundings
 // of these few operations (each <= 6e-8 relative, a dozen of them): every bound is pushed outwards by it at every use.
-constexpr float kQ8Rho = 4e-6f, kQ8Eta = 1e-17f;
+// (kQ8Rho, kQ8Eta: declared beside the minfo layout.)
 
 __device__ __forceinline__ void refine_q8_body(
     const BatchPtrs& P, int B, int64_t ldq, int nq, int64_t ldt, int nt, int tiles, const int* __restrict__ minfo, const unsigned char* __restrict__ qi8,
@@ -3155,15 +3173,18 @@ __device__ __forceinline__ void refine_q8_body(
     }
     auto slot_of = [&](int k) { return 3 * (sl + 16 * (k / 3)) + k % 3; };
     // the pair's grid and this query's slack, in units of s
-    const float sf = __int_as_float(minfo[kMinfoQ8S + pb]), lof = __int_as_float(minfo[kMinfoQ8Lo + pb]);
-    const float te2 = __int_as_float(minfo[kMinfoTerr + pb]);
-    const float inv_s = 1.f / sf;
-    const float eta_s = kQ8Eta * inv_s;
+    // (the pair's share of it — 1 / s, eta / s, the square root of the train residual te2 = kMinfoTerr, the term in mabs — is
+    // reduce_modes' work, once per pair: scalar loads here)
+    const float inv_s = __int_as_float(minfo[kMinfoQ8InvS + pb]);
+    const float eta_s = __int_as_float(minfo[kMinfoQ8EtaS + pb]);
     float e_s;
     {
-        const float mabs = fmaxf(fabsf(lof), fabsf(lof + 255.f * sf));
-        // residual norms: float32 sums (<= 12 roundings) of differences each within 2^-24 mabs of the real one
-        const float E = (sqrtf(qe2) + sqrtf(te2)) * (1.f + 8e-6f) + 24.f * 5.9604645e-08f * mabs * (1.f + 1e-6f);
+        // residual norms: float32 sums (<= 12 roundings) of differences each within 2^-24 mabs of the real one,
+        // mabs = max(|lo|, |lo + 255 s|).  E is, operation for operation,
+        //   const float E = (sqrtf(qe2) + sqrtf(te2)) * (1.f + 8e-6f) + 24.f * 5.9604645e-08f * mabs * (1.f + 1e-6f);
+        // with sqrtf(te2) and the product after the last + read from minfo
+        const float te_rt = __int_as_float(minfo[kMinfoQ8TeRt + pb]), e_abs = __int_as_float(minfo[kMinfoQ8Abs + pb]);
+        const float E = (sqrtf(qe2) + te_rt) * (1.f + 8e-6f) + e_abs;
         e_s = E * inv_s * (1.f + 1e-6f);
         if (!(e_s < 1e30f)) e_s = kInf;                          // (NaN / inf residuals: nothing is ever certified or skipped)
     }
@@ -3200,15 +3221,22 @@ __device__ __forceinline__ void refine_q8_body(
     // record threshold (keys) and row threshold (D) from the second smallest record key; every record when there are fewer than two
     int thr = kKeyEmptyI - 1;
     int dlim = INT_MAX;                                          // rows with D <= dlim are evaluated in float32
+    // 32-bit integers suffice for U, al and hides_nothing's dlow: cq = wq - 128 with 0 <= wq <= 128 * 128^2 = 2^21; a key's acc = key >> 8 is sum ab + C with |sum ab| <= 2^21 and C in [kI8CMin, kI8CMax], so |acc| < 2^22 — and the
+    // sentinels INT_MAX, kKeyEmptyI shift to < 2^23, which covers the lanes whose result is discarded; |base| < 2^21 (a train
+    // row's floor(w / 2) <= 2^20, nudged by at most the init product's range).  So |cq + 2 (acc + base) + 1| < 2^21 + 2 (2^23 +
+    // 2^21) + 1 < 2^25 on every lane, and with 0 <= dlim < 2^24 also |((dlim - cq) >> 1) - base + 1| < 2^24: nothing wraps, and
+    // (float) of an int and of a long long of the same value round alike.
+    static_assert(kDim == 128 && kI8CMax < (1 << 19) && kI8CMin > -(1 << 19) && (kKeyEmptyI >> 8) < (1 << 23), "the 32-bit ranges above");
     if (a2 < kKeyEmptyI) {
-        const long long U = (long long)cq + 2 * ((long long)(a2 >> 8) + base) + 1;
+        const int U = cq + 2 * ((a2 >> 8) + base) + 1;
         const float R = (sqrtf((float)(U > 0 ? U : 0)) * (1.f + 2e-7f) + e_s) * (1.f + kQ8Rho) + eta_s;
         const float dl = dlim_of(R);
         if (dl < 1.6e7f) {                                       // (D < 2^23 for every row: a larger bound limits nothing)
             dlim = (int)dl;
             // a row with D <= dlim has acc <= al (D >= cq + 2 (acc + base)); integer arithmetic from here on
-            const long long al = (((long long)dlim - cq) >> 1) - base + 1;
-            if (al < 8388606) thr = (int)((((unsigned)(int)al) << 8) | 0xFFu);
+            // (the value of `const long long al = (((long long)dlim - cq) >> 1) - base + 1;` — see the ranges above)
+            const int al = ((dlim - cq) >> 1) - base + 1;
+            if (al < 8388606) thr = (int)((((unsigned)al) << 8) | 0xFFu);
         }
         if (thr < a2) thr = a2;                                  // (never below the two records the bound came from)
     }
@@ -3263,9 +3291,11 @@ __device__ __forceinline__ void refine_q8_body(
         for (int e0 = 0; e0 < nmax; e0 += 4) {
             const int e = e0 + (sl >> 2);
             const int row = e < nqual ? myqual[e] : -1;
-            const float* const trow[1] = {row >= 0 ? T + (int64_t)row * ldt : nullptr};
+            // an idle quad reads row 0 (nt >= 1 here) and its sum is dropped by the test below, as int_row's idle lanes read tile 0
+            // (a guard per load costs eight exec-masked regions and 32 zeroing moves per pass)
+            const float* const trow[1] = {T + (int64_t)max(row, 0) * ldt};
             float out[1];
-            exact_l2sq_quad_rows<1, true>(qrows + ql * kDim, trow, sl & 3, out);
+            exact_l2sq_quad_rows<1, false>(qrows + ql * kDim, trow, sl & 3, out);
             if ((sl & 3) == 2 && row >= 0) best2_insert_unique(b, sqrtf(out[0]), row);
         }
         best2_reduce16_from_quad_lane2(b);
@@ -3395,7 +3425,7 @@ __device__ __forceinline__ void refine_q8_body(
     // certificate: does the stream with third key `key3` provably hide nothing closer than the answer's second distance?
     auto hides_nothing = [&](int key3, float d2c) -> bool {
         if (key3 >= kKeyEmptyI) return true;                       // fewer than three records: the stream discarded nothing
-        const long long dlow = (long long)cq + 2 * ((long long)(key3 >> 8) + base);
+        const int dlow = cq + 2 * ((key3 >> 8) + base);          // (32 bits suffice: the ranges beside U)
         const float lowb = (sqrtf((float)(dlow > 0 ? dlow : 0)) * (1.f - 2e-7f) - e_s) * (1.f - kQ8Rho) - eta_s;
         return lowb > d2c * inv_s * (1.f + 1e-6f);                 // (d2c = +inf while fewer than two rows are known, e_s = +inf: false)
     };
