@@ -710,15 +710,18 @@ __device__ __forceinline__ uint2 frag_init_operand(float x, bool query_side, int
 //     d^2 = c_q - 128 + (w_t & 1) + 2 (acc + base):   the filter ranks by acc, which is the exact order up to the parity bit.
 // The refine kernel's certificate is therefore an INTEGER one with slack 1 (+ 2 for float32 square roots that collide):
 // no epsilon, no error budget, no assumption about the matrix pipe's rounding.
-// Init product (one MFMA per tile, K = 32): query side {1, -128 x 31}, train side {C & 127, digits d_k} with
-// sum d_k = -(C >> 7), d_k in [-128, 127]:  C in [-503 936, 508 031].  Pairs whose floor(w_t / 2) spread exceeds that range
-// (possible only when all-127 and all-0 / all-255 rows meet in one image) fall back to the fp16 body, as do non-u8 data.
+// C_t reaches the accumulators as a plain integer: the tile's ninth KiB holds int C[32] (one per row, written by
+// knn_split_images_kernel), the filter stages it through a small LDS ring and reads it straight into the register block that is
+// SrcC of the groups' first products (filter_i8_body).  The admitted range is still the one of the base-128 digit encoding that
+// an init MFMA used to decode, C in [-503 936, 508 031]: pairs whose floor(w_t / 2) spread exceeds it (possible only when all-127
+// and all-0 / all-255 rows meet in one image) fall back to the fp16 body, as do non-u8 data — no input changes body.
 constexpr int kI8Groups = 8;                                // 32-query groups per wave
 constexpr int kI8Rows = 4 * kI8Groups * 32;                 // 1024 queries per workgroup (row block of the i8 partition)
 constexpr int kI8SubTiles = 128;                            // tiles per substream: the key's low 8 bits are (tile inside it) << 1 | register half
-constexpr int kI8TileBytes = 5 * 1024;                      // train image per 32 rows: 4 k-steps of 32 ([64 lanes][16 B]) + the init fragment
+constexpr int kI8TileBytes = 5 * 1024;                      // train image per 32 rows: 4 k-steps of 32 ([64 lanes][16 B]) + a KiB whose first 128 B are int C[32]
+constexpr int kI8COff = 4 * 1024;                           // byte offset of C[32] inside a tile
 constexpr int kI8QTileBytes = 4 * 1024;                     // query image per 32 rows
-constexpr int kI8CMax = 508031, kI8CMin = -503936;          // range of the init product
+constexpr int kI8CMax = 508031, kI8CMin = -503936;          // admitted range of C_t (see above)
 static_assert(kI8SubTiles == kI8SubTilesHost, "make_plan's copy");
 constexpr int kKeyEmptyI = 0x7FFFFF00;                      // i8 keys >= this are empty slots / the first tile's pretend "previous tile"
 
@@ -1256,22 +1259,6 @@ __global__ __launch_bounds__(kPrepThreads) void knn_prep_kernel(BatchPtrs P, int
     }
 }
 
-// Train side of the i8 init product for C in [kI8CMin, kI8CMax]: slot 0 (byte 0 of the h = 0 lanes; query side 1) holds C & 127,
-// the other 31 slots (query side -128) hold digits d_k in [-128, 127] with sum d_k = -(C >> 7), dealt greedily in slot order.
-__device__ __forceinline__ uint4 frag_init_i8(int C, int h) {
-    int S = -(C >> 7);                                         // what slots 1 .. 31 must add up to
-    if (h == 1) S -= max(-15 * 128, min(15 * 127, S));         // (slots 1 .. 15 live in the h = 0 lanes)
-    unsigned wds[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        int d;
-        if (h == 0 && k == 0) d = C & 127;
-        else { d = max(-128, min(127, S)); S -= d; }
-        wds[k >> 2] |= (unsigned)(d & 0xFF) << (8 * (k & 3));
-    }
-    return make_uint4(wds[0], wds[1], wds[2], wds[3]);
-}
-
 // The bf16 (hi, mid) planes of the images, for the split arithmetic only: every workgroup derives the batch's mode from
 // the flags the prep launch left (as the filter will) and returns at once unless it is the split mode.
 // (A small grid — one 512-thread workgroup per CU, every one loops over the pairs: launching the waves of a prep-sized
@@ -1481,22 +1468,21 @@ __global__ __launch_bounds__(kSplitThreads) void knn_split_images_kernel(BatchPt
     for (int b = 0; b < B; ++b) mode = max(mode, smode[b]);
     // (repaired: workgroup 0's view of the modes is the one from BEFORE the repair — the last workgroup out has written them)
     if (!repaired && blockIdx.x == 0 && threadIdx.x == 0) minfo[kMinfoBatchMode] = mode;
-    // The integer body's init fragments (frag_init_i8: the digits of floor(w_t / 2) - base) need the pair's base, so they are
-    // written here, not by the prep pass.
+    // The integer body's row terms C_t = floor(w_t / 2) - base need the pair's base, so they are written here, not by the prep
+    // pass: one int per row into the first 128 bytes of the tile's ninth KiB (the rest of that KiB is never read), kI8CMax for
+    // the padding rows of the last tile.
     if (!repaired && blockIdx.x == 0 && threadIdx.x < kMaxBatch + 1) {
         if (threadIdx.x == kMaxBatch) { minfo[kMinfoI8] = i8 ? 1 : 0; minfo[kMinfoQ8] = (i8 && q8any) ? 1 : 0; }
         else if (threadIdx.x < B && ti8) minfo[kMinfoBase + threadIdx.x] = s8base[threadIdx.x];
     }
     if (i8) {
-        // one flat loop over (pair, row, half-wave): every load of the launch is in flight at once (a loop over the pairs was a
+        // one flat loop over (pair, row): every load of the launch is in flight at once (a loop over the pairs was a
         // dependent round trip per pair: 9 us for a batch of 8)
-        const int per_pair = 2 * nt_pad;
-        for (int e = blockIdx.x * kSplitThreads + threadIdx.x; e < B * per_pair; e += gridDim.x * kSplitThreads) {
-            const int pb = e / per_pair, x = e - pb * per_pair;
-            const int r = x >> 1, h = x & 1;
+        for (int e = blockIdx.x * kSplitThreads + threadIdx.x; e < B * nt_pad; e += gridDim.x * kSplitThreads) {
+            const int pb = e / nt_pad, r = e - pb * nt_pad;
             const int wv = r < nt ? wt[pb * s_tn + r] : 0;
-            *reinterpret_cast<uint4*>(ti8 + pb * s_ti8 + (int64_t)(r >> 5) * kI8TileBytes + 4 * 1024 + ((h * 32 + (r & 31)) << 4)) =
-                frag_init_i8(r < nt ? (wv >> 1) - s8base[pb] : kI8CMax, h);
+            *reinterpret_cast<int*>(ti8 + pb * s_ti8 + (int64_t)(r >> 5) * kI8TileBytes + kI8COff + 4 * (r & 31)) =
+                r < nt ? (wv >> 1) - s8base[pb] : kI8CMax;
         }
         return;
     }
@@ -2035,7 +2021,7 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define SFM_MFMA_F16(acc, a, b) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b))
 #define SFM_MFMA_BF16(acc, a, b) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b))
 #define SFM_MFMA_BF16_INIT(acc, a, b) asm volatile("v_mfma_f32_32x32x8_bf16 %0, %1, %2, 0" : "=v"(acc) : "v"(a), "a"(b))
-#define SFM_MFMA_BF16_REINIT(acc, a, b) asm volatile("v_mfma_f32_32x32x8_bf16 %0, %1, %2, 0" : "+v"(acc) : "v"(a), "a"(b))   // in-loop: pins the register block (see SFM_MFMA_I8_REINIT)
+#define SFM_MFMA_BF16_REINIT(acc, a, b) asm volatile("v_mfma_f32_32x32x8_bf16 %0, %1, %2, 0" : "+v"(acc) : "v"(a), "a"(b))   // in-loop: pins the register block ("+v": the old values count as read; see SFM_I8_CREG)
 // first product of a chain: D = A B + C with C a DIFFERENT register block (the tile's shared init values); D is early-clobber —
 // an MFMA's D may coincide with its C exactly or not at all
 #define SFM_MFMA_F16_C(acc, a, b, c) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(acc) : "v"(a), "a"(b), "v"(c))
@@ -2323,19 +2309,25 @@ __device__ __forceinline__ void filter_q4_body(
 //     refine kernel then reads 16 rows per record — its L1 traffic doubled and it lost more than the filter gained);
 //     the key's low 8 bits are (tile inside a 128-tile substream) << 1 | e;
 //   * i32 accumulation: scores are exact (up to the parity bit, see the images' comment), keys hold the whole score
-//     (acc << 8 | tile), the accumulator init is one i8 MFMA per tile shared by the 8 groups (C operand of their first products);
+//     (acc << 8 | tile), the accumulators start from the tile's row terms C (C operand of the 8 groups' first products), which
+//     come as 32 plain integers per tile through a per-wave LDS ring — see "row terms" in the body;
 //   * records are the three packed keys per stream and half-wave, ONE 16-byte slot per query ([row block][stream][h][1024
 //     queries][3 keys + pad]: a store instruction writes 512 contiguous bytes per half-wave) — see the flush below.
 // Row blocks are 1024 queries; the partition tables are those of the i8 plan (wg_begin8 ...).
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 #define SFM_MFMA_I8(acc, a, b) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b))
-#define SFM_MFMA_I8_C(acc, a, b, c) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %3" : "=&v"(acc) : "v"(a), "a"(b), "v"(c))
-#define SFM_MFMA_I8_INIT(acc, a, b) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=v"(acc) : "v"(a), "a"(b))
-// The in-loop form declares the old values read ("+v") although the instruction does not read them: the tile's init values
-// must keep ONE register block for the whole loop.  With "=v" the old block is dead after the last chain's first MFMA has
-// been ISSUED, and hipcc hands its registers to the epilogue's temporaries — written by the vector ALU while that MFMA is still
-// reading them as SrcC (no hardware interlock: results of a whole query group went wrong, found by tests/test_gpu_knn_i8.py).
-#define SFM_MFMA_I8_REINIT(acc, a, b) asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "+v"(acc) : "v"(a), "a"(b))
+// The tile's row terms C (SrcC of the eight groups' first products) live in ONE fixed register block for the whole kernel body,
+// v[2:17], named in the statements themselves: four ds_read_b128 fill its quarters (an inline-asm operand cannot name a part of
+// a 16-register value), and every statement that touches the block declares it read AND written ("+").  The block is therefore
+// live from the segment's first read to its last product and hipcc can hand none of its registers to the epilogue's
+// temporaries: with a plain output the old values were dead once the last chain's first MFMA had been ISSUED, and a temporary
+// was written by the vector ALU while that MFMA was still reading the block as SrcC (no hardware interlock: results of a whole
+// query group went wrong, found by tests/test_gpu_knn_i8.py on the init MFMA this replaces).
+#define SFM_I8_CREG "{v[2:17]}"
+#define SFM_MFMA_I8_CP(acc, a, b, c) asm volatile("v_mfma_i32_32x32x32_i8 %0, %2, %3, %1" : "=&v"(acc), "+" SFM_I8_CREG(c) : "v"(a), "a"(b))
+// quarter q (0 .. 3) of the block <- 16 bytes of LDS at addr + off
+#define SFM_I8_CREAD(c, q, addr, off)                                                                                      \
+    asm volatile("ds_read_b128 v[%c2:%c3], %1 offset:%c4" : "+" SFM_I8_CREG(c) : "v"(addr), "n"(2 + 4 * (q)), "n"(5 + 4 * (q)), "n"(off) : "memory")
 
 // (plain C++: hipcc emits the single v_lshl_or_b32 with the scalar seq.  As an asm statement the pack DEFINED a register of an
 // inline asm, and hipcc's hazard recogniser put an s_nop before the first compiler-emitted VALU that read it.)
@@ -2362,6 +2354,17 @@ __device__ __forceinline__ void filter_i8_body(
     auto train_off = [](int l) { return ((l & ~12) | ((l & 4) << 1) | ((l & 8) >> 1)) * 16; };
     const int voff_t = train_off(lane);
     const int qtiles = nq_pad >> 5;
+    // ---- row terms.  Accumulator register r of half-wave h holds tile row 16 (r >> 3) + 8 h + (r & 7) (above), so a lane needs
+    // C[8 h .. 8 h + 7] and C[16 + 8 h .. 16 + 8 h + 7] of the tile's int C[32]: four 16-byte LDS reads, the same address in
+    // every lane of a half-wave (broadcasts).  The integers come through a ring of two 256-byte slots per wave, private to the
+    // wave: ONE LDS-DMA load per round of two tiles, lanes 0-31 fetching the 32 integers of the round's first tile and lanes
+    // 32-63 those of its second (lane-linear in the slot: tile parity p at 128 p).  Round R (tiles 2 R, 2 R + 1 of the segment)
+    // uses slot R & 1.  Tile i reads the terms of tile i + 1 in its phase B; the DMA of round R is issued in the phase B of tile
+    // 2 R - 3 (rounds 0 and 1: before the segment's first fragment loads).  How the two hardware rules are met is stated at the
+    // DMA and at the reads in tile().
+    __shared__ __attribute__((aligned(512))) int cring[4][2][64];   // (512: slots are switched by an XOR)
+    const unsigned ring = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) int*)&cring[0][0][0]) + (unsigned)wave * 512u;
+    const int voff_c = h * kI8TileBytes + kI8COff + 4 * j;
 
     while (u < u_end) {
         const int rb = __builtin_amdgcn_readfirstlane((int)(u / tiles));
@@ -2377,21 +2380,29 @@ __device__ __forceinline__ void filter_i8_body(
         const int qg0 = rbl * (kI8Rows / 32) + wave * NG;                      // first 32-query tile of this wave
         const int qloc0 = wave * NG * 32 + j;                                  // query inside the row block; group g adds 32 g
 
-        // ---- train fragments of the first D tiles (init fragment first: it is consumed first), then the query fragments
-        i32x4 fr[D][5];
+        // ---- row terms of rounds 0 and 1 (ring slots 0 and 1), then the train fragments of the first D tiles and the query
+        // fragments.  A DMA's first tile is clamped to the segment's last one the way ld_off is: the terms of a tile past the
+        // segment are fetched (from inside the image, or dropped by the resource's range check) and never read.
+        // The ring was last read in the previous segment's last tile, by reads an lgkmcnt(0) there retired; its DMAs still in
+        // flight land before these (one wave's loads return in order).
+        const int ld_last = __builtin_amdgcn_readfirstlane((t_end - 1) * kI8TileBytes);
+        auto stage_c = [&](unsigned slot_addr /*wave-uniform*/, int off /*wave-uniform*/) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(trs, (lptr_t)(size_t)slot_addr, 4, voff_c, off, 0, 0);
+        };
+        stage_c(ring, __builtin_amdgcn_readfirstlane(t_begin * kI8TileBytes));
+        stage_c(ring + 256u, __builtin_amdgcn_readfirstlane(min((t_begin + 2) * kI8TileBytes, ld_last)));
+        i32x4 fr[D][4];
         auto load_frag = [&](int s_, int f, int tile_, bool live, bool in_loop = false) {
             if ((ABL & 1) && in_loop) return;
             const int tile = live ? tile_ : t_end - 1;
             fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t, __builtin_amdgcn_readfirstlane(tile * kI8TileBytes + f * 1024), 0);
         };
 #pragma unroll
-        for (int d = 0; d < D; ++d) {
-            load_frag(d, 4, t_begin + d, t_begin + d < t_end);
+        for (int d = 0; d < D; ++d)
 #pragma unroll
             for (int f = 0; f < 4; ++f) load_frag(d, f, t_begin + d, t_begin + d < t_end);
-        }
         __builtin_amdgcn_sched_barrier(0);
-        u32x4 bq[NG][4], bi;
+        u32x4 bq[NG][4];
         {
             i32x4 tmp[NG][4];
             // lane * 16 again, from voff_t (bits 6 and 7 swapped back) behind an opaque copy: formed from `lane` it is hoisted out
@@ -2410,8 +2421,6 @@ __device__ __forceinline__ void filter_i8_body(
             for (int g = 0; g < NG; ++g)
 #pragma unroll
                 for (int f = 0; f < 4; ++f) asm volatile("" : "=a"(bq[g][f]) : "0"(__builtin_bit_cast(u32x4, tmp[g][f])));
-            // query side of the init product: slot 0 (byte 0 of the h = 0 lanes) = 1, the other 31 slots = -128
-            asm volatile("" : "=a"(bi) : "0"(u32x4{h ? 0x80808080u : 0x80808001u, 0x80808080u, 0x80808080u, 0x80808080u}));
         }
         asm volatile("s_nop 4");                                               // v_accvgpr_write -> MFMA operand
 
@@ -2449,8 +2458,16 @@ __device__ __forceinline__ void filter_i8_body(
         for (int g = P; g < NG; ++g)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[g][r] = 0x7FFFFF;
-        SFM_MFMA_I8_INIT(cinit, __builtin_bit_cast(u32x4, fr[0][4]), bi);
-        asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+        // The first tile's row terms (slot 0, parity 0).  Every load of the prologue is younger than the two DMAs and the query
+        // fragments have been waited for above, so the vmcnt(0) costs nothing and makes the order explicit; the previous
+        // segment's last SrcC readers are long through (its closing s_nops and epilogue).
+        // caddr: this lane's read address in the slot that the next even tile (slot_c 0) reads from; see tile().
+        int caddr = (int)ring + 32 * h;
+        asm volatile("s_waitcnt vmcnt(0)\n\t"
+                     "ds_read_b128 v[2:5], %1\n\tds_read_b128 v[6:9], %1 offset:16\n\t"
+                     "ds_read_b128 v[10:13], %1 offset:64\n\tds_read_b128 v[14:17], %1 offset:80\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=" SFM_I8_CREG(cinit) : "v"(caddr) : "memory");
 
         // Rows past the last train (the train image is padded to whole tiles) must never make a key: a record's score has to be
         // the score of a REAL row of the record (the refine kernel's selection argument counts distinct real rows).  The last,
@@ -2486,15 +2503,17 @@ __device__ __forceinline__ void filter_i8_body(
         // Scalars of the tile loop are carried and advanced by additions, each written into the gap that has room for it (a gap
         // hides five to six single-issue instructions beside its MFMA, the four of a piece included):
         //   ld_off  byte offset of the tile whose fragments tile t refills, min(t + D, t_end - 1) tiles into the image;
-        //   sq, sq1 (tile in substream) << 1 of the tile before t (0 before a segment's first) and sq | 1;  sq_n: the same of t.
-        const int ld_last = __builtin_amdgcn_readfirstlane((t_end - 1) * kI8TileBytes);
+        //   sq, sq1 (tile in substream) << 1 of the tile before t (0 before a segment's first) and sq | 1;  sq_n: the same of t;
+        //   c_off   byte offset of the first tile of the round whose row terms the next odd tile stages (min(.., ld_last)),
+        //   c_dst   the ring slot they go to.
         int ld_off = __builtin_amdgcn_readfirstlane(min(t_begin + D - 1, t_end - 1) * kI8TileBytes);
         int sq = 0, sq1 = 1, sq_n = 0;
-        auto load_next = [&](int s_, int f, int off, int off4) {
+        int c_off = __builtin_amdgcn_readfirstlane(min((t_begin + 4) * kI8TileBytes, ld_last));
+        unsigned c_dst = ring;
+        auto load_next = [&](int s_, int f, int off) {
             if (ABL & 1) return;
-            // (fragments 0 .. 3 through the instruction's immediate offset: no scalar addition per load)
-            if (f < 4) fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t + f * 1024, off, 0);
-            else fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t, off4, 0);
+            // (through the instruction's immediate offset: no scalar addition per load)
+            fr[s_][f] = __builtin_amdgcn_raw_buffer_load_b128(trs, voff_t + f * 1024, off, 0);
         };
         auto tile = [&](int t, auto slot_c, auto flush_c, auto tail_c) {
             constexpr int S = decltype(slot_c)::value;
@@ -2502,7 +2521,6 @@ __device__ __forceinline__ void filter_i8_body(
             constexpr int TL = decltype(tail_c)::value;             // 0: t is never the train image's partial last tile (no test, no mask code); 2: tested
             const int seq_prev = sq, seq_prev1 = sq1;
             const bool part_cur = TL == 2 && nrem != 0 && t + 1 == tiles;   // (wave-uniform) t is the train image's last, partial tile; its second-half groups' epilogue is the tail's
-            int off4 = 0;
             // ---- phase A: chains of groups 0 .. 3; k-step st carries the epilogue of group P + st (previous tile)
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
@@ -2510,11 +2528,13 @@ __device__ __forceinline__ void filter_i8_body(
 #pragma unroll
                 for (int g = 0; g < P; ++g) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (st == 0) SFM_MFMA_I8_C(acc[g], a, bq[g][st], cinit);
+                    if (st == 0) SFM_MFMA_I8_CP(acc[g], a, bq[g][st], cinit);
                     else SFM_MFMA_I8(acc[g], a, bq[g][st]);
                     epi(g, acc[P + st], seq_prev, seq_prev1, k0[P + st], k1[P + st], k2[P + st], false);
                     if (st == 0 && g == 1) ld_off = __builtin_amdgcn_readfirstlane(min(ld_off + kI8TileBytes, ld_last));
-                    if (st == 1 && g == 1) off4 = __builtin_amdgcn_readfirstlane(ld_off + 4 * 1024);
+                    // (odd tile: on to the slot of the NEXT round, whose first tile's terms this tile reads; the even tile
+                    // behind it reads the same slot's second half)
+                    if (st == 1 && g == 1 && S == 1) caddr ^= 256;
                     if (st == 2 && g == 1 && FL == 0) { sq = sq_n; sq1 = __builtin_amdgcn_readfirstlane(sq_n | 1); }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -2531,37 +2551,53 @@ __device__ __forceinline__ void filter_i8_body(
                 sq1 = __builtin_amdgcn_readfirstlane(sq_n | 1);
             }
             const int seq_cur = sq, seq_cur1 = sq1;
-            // ---- phase B: chains of groups 4 .. 7 and the NEXT tile's init MFMA (two MFMAs after the last reader of the current
-            // values): 17 MFMAs.  The 16 pieces of the epilogue of groups 0 .. 3 (this tile: complete since phase A) follow the
-            // first 16, so the gap behind the last MFMA — the one that crosses into the next tile, or the back edge — holds the
-            // last fragment load, the next tile's first wait and the loop control only.  The fragments die one by one and are
+            // ---- phase B: chains of groups 4 .. 7, the 16 pieces of the epilogue of groups 0 .. 3 (this tile: complete since
+            // phase A) and the NEXT tile's row terms, read from the ring into cinit.  The fragments die one by one and are
             // refilled for tile t + D.
+            // Rule "no interlock on SrcC" (cinit is SrcC of this phase's first four MFMAs): the first read that overwrites a
+            // quarter of cinit is issued behind the second MFMA after the last of them (k-step 1, group 1: where the init MFMA
+            // this replaces sat, and an LDS read returns later than that MFMA wrote), the other three one gap later each; the
+            // lgkmcnt(0) that retires all four sits in the tile's LAST gap, seven MFMAs behind the last read and directly ahead
+            // of the next tile's first SrcC reader: beside another launch set's refine the LDS answers late, and with the wait
+            // three gaps earlier the step ran 1.3 % slower than the parent's where this placement runs 1.3 % faster (docs/knn.md).
+            // cinit never leaves v[2:17] (SFM_I8_CREG).
+            // Rule "read a staged slot one phase after the wait that retires it": the slot read here was staged by the DMA of
+            // tile t - 2 (odd t: the first half of the next round's slot) or t - 3 (even t: the second half of this round's),
+            // issued BEFORE that tile's load of fragment 3 (or by the segment's prologue, before every fragment load).  The load
+            // of fragment 3 in tile t - 2 filled fr[S][3], which this tile's phase A has consumed behind hipcc's counted vmcnt.
+            // One wave's loads return in order and the ring is private to the wave, so the DMA had landed before phase A's last
+            // k-step, a phase before these reads.  The DMA below (odd t) restages the slot that tile t - 1 read last: those
+            // reads were retired by that tile's lgkmcnt(0).
             __builtin_amdgcn_sched_barrier(0);
-            load_next(S, 4, ld_off, off4);
             int n = 0;                                             // MFMAs of this phase so far
             auto piece_b = [&]() {
-                if (n < 16) epi(n & 3, acc[n >> 2], seq_cur, seq_cur1, k0[n >> 2], k1[n >> 2], k2[n >> 2], part_cur);
+                epi(n & 3, acc[n >> 2], seq_cur, seq_cur1, k0[n >> 2], k1[n >> 2], k2[n >> 2], part_cur);
                 ++n;
             };
+            constexpr int kHalf = S == 0 ? 128 : 0;                // the next tile is the second (even t) / first (odd t) of its round
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
                 const u32x4 a = __builtin_bit_cast(u32x4, fr[S][st]);
 #pragma unroll
                 for (int g = 0; g < P; ++g) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (st == 0) SFM_MFMA_I8_C(acc[P + g], a, bq[P + g][st], cinit);
+                    if (st == 0) SFM_MFMA_I8_CP(acc[P + g], a, bq[P + g][st], cinit);
                     else SFM_MFMA_I8(acc[P + g], a, bq[P + g][st]);
                     piece_b();
-                    if (st == 1 && g == 1) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        SFM_MFMA_I8_REINIT(cinit, __builtin_bit_cast(u32x4, fr[(S + 1) % D][4]), bi);
-                        __builtin_amdgcn_sched_barrier(0);
-                        piece_b();
-                    }
+                    if (st == 1 && g == 1) SFM_I8_CREAD(cinit, 0, caddr, kHalf);
+                    if (st == 1 && g == 2) SFM_I8_CREAD(cinit, 1, caddr, kHalf + 16);
+                    if (st == 1 && g == 3) SFM_I8_CREAD(cinit, 2, caddr, kHalf + 64);
+                    if (st == 2 && g == 0) SFM_I8_CREAD(cinit, 3, caddr, kHalf + 80);
                     if (st == 2 && g == 1) sq_n = __builtin_amdgcn_readfirstlane(sq_n + 2);
+                    if (S == 1 && !(ABL & 1)) {                    // the row terms of the round after next, one DMA per round
+                        if (st == 3 && g == 1) stage_c(c_dst, c_off);
+                        if (st == 3 && g == 2) c_off = __builtin_amdgcn_readfirstlane(min(c_off + 2 * kI8TileBytes, ld_last));
+                        if (st == 3 && g == 3) c_dst ^= 256u;
+                    }
+                    if (st == 3 && g == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+" SFM_I8_CREG(cinit) : : "memory");
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                load_next(S, st, ld_off, off4);
+                load_next(S, st, ld_off);
             }
         };
         // whole rounds of D tiles, the remainder after the loop (see the fp16 body: hipcc's waitcnt merge at the back edge).
