@@ -1439,6 +1439,71 @@ int sfm_verify_lo_pick(const uint64_t* top_dev, const double* E_lo_dev, const in
                        void* stream);
 int sfm_host_verify_refit(const double* M81_host, double* E_host);
 
+/* ------------------------------------------------------------------------
+ * VERIFY-H (csrc/verify_h.hip, docs/tracks.md section 13): a homography per pair beside VERIFY's essential matrix, from the same survivors
+ * and the same samples, so that a caller can tell the pairs whose essential matrix is not determined (one plane, no baseline).  Three
+ * launches per chunk of pairs, on the caller's stream, no host wait.  Arithmetic as VERIFY: float64, correctly rounded, in the order
+ * written, no FMA, only + - * / sqrt fabs and comparisons; every integer output is a count, a maximum of a key or a copy.
+ * tests/np_verify_h.py restates every output word.  surv, m, m', pair_img, img_off, xn, samp and "valid" survivors: as VERIFY.
+ *
+ * sfm_verify_h_models — one lane per sample.  Sample s of pair p is the FIRST FOUR slots of samp[p][s] (sfm_verify_samples; there is no
+ *   second sampler).  It is valid when both images are in range, m' >= 5, each of the four slots is in 0..m'-1 and both nodes of each of
+ *   the four survivors lie in 0..n_nodes-1.  A valid sample runs homography4 (below) on x1 = xn of the four first nodes, x2 = xn of the
+ *   four second nodes.  ok_dev int32 [n_pairs][H]: 1 with a model, else 0;  Hm_dev float64 [n_pairs][H][9]: the model (Hm[8] = 1), zero
+ *   without one.  72 + 4 + 4 (counts) = 80 bytes a sample.
+ *
+ * homography4(x1, x2) = sfm_host_homography4(x1_host, x2_host, H_host) (x: four points, (a, b) interleaved; H_host all zero: no model):
+ *   the 8 x 9 augmented system of h8 = 1; match k = 0..3 gives row 2k = (a1, b1, 1, 0, 0, 0, -(a2 a1), -(a2 b1) | a2) and row 2k + 1 =
+ *   (0, 0, 0, a1, b1, 1, -(b2 a1), -(b2 b1) | b2).  For col = 0..7: the pivot row is the row r >= col with the largest |A[r][col]| under
+ *   the comparison v > largest-so-far, r ascending from col (the lowest row on ties; a NaN never wins); it is swapped with row col;
+ *   d = A[col][col]; d == 0: no model; for r = col+1..7: f = A[r][col] / d, A[r][k] = A[r][k] - f * A[col][k] for k = col+1..8.
+ *   Then for col = 7..0: s = A[col][8]; s = s - A[col][k] * h[k] for k = col+1..7 ascending; h[col] = s / A[col][col].  h[8] = 1.
+ *   A non-finite word among h[0..7]: no model.
+ *
+ * sfm_verify_h_score — over the first m' survivors of the pair whose two nodes are valid, for every sample with ok != 0:
+ *     w = H6 a1 + H7 b1 + H8;  u = (H0 a1 + H1 b1 + H2) / w;  v = (H3 a1 + H4 b1 + H5) / w         (left to right)
+ *     d = (u - a2) * (u - a2) + (v - b2) * (v - b2);   inlier  <=>  w > 0 and (float)d <= thr2h
+ *   counts_dev int32 [n_pairs][H]: the inlier count, 0 for a sample without a model.  best_dev uint64 [n_pairs]: the maximum over the
+ *   pair's models of ((uint32)count << 32) | (0xFFFFFFFF - s): the largest count, then the lowest sample; 0 without a model.
+ *
+ * sfm_verify_h_select — per pair.  Without a model (best = 0, or its sample >= H): keep_h row, H_out and sv zero, h_info = (m, 0, 0, 0,
+ *   -1, -1, 0, status | 2).  Otherwise, with n(G) the number of valid survivors e < m' with q < cap that are inliers of G at thr2h:
+ *     1. Hs = Hm of the best sample;  n_s = n(Hs).
+ *     2. when refit == 1 and n_s >= 8: per inlier of Hs, r1 = (-a1, -b1, -1, 0, 0, 0, a2 a1, a2 b1, a2) and r2 = (0, 0, 0, -a1, -b1, -1,
+ *        b2 a1, b2 b1, b2);  M[i][j] = M[j][i] = the sum over the inliers of (r1[i] * r1[j] + r2[i] * r2[j]), i <= j, in VERIFY-LO's order:
+ *        s_l (l = 0..255) starts at 0 and takes its survivors e = l, l + 256, .. < m' ascending, then for h = 1, 2, 4, .. 128:
+ *        s_l = s_l + s_(l + h) for every l that is a multiple of 2 h;  M[i][j] = s_0.
+ *        c = sfm_host_verify_h_refit(M): cv::SVD's one-sided Jacobi on the rows a_i[k] = M[k][i], row 8 of vt (the right singular vector
+ *        of the smallest singular value), nine words.  A non-finite word in c: the refit is dropped.  The sign of a null vector is
+ *        arbitrary, and -c has the u, v and d of c with w of the other sign, so one pass counts both: n_pos = n(c), n_neg = n(-c);
+ *        Hr = -c when n_neg > n_pos, else c;  n_r = max(n_pos, n_neg).
+ *     3. the winner Hw = Hr when n_r > n_s (strictly), else Hs: the final count is never below the sample's.
+ *     4. (W0 >= W1 >= W2) = the singular values of cv::SVD's Jacobi on Hw (rows a_i[k] = Hw[k][i]);  H_out = Hw / W1 word by word;
+ *        sv = (W0 / W1, W1 / W1, W2 / W1)  (= sfm_host_verify_h_normalise).
+ *     5. every inlier of Hw has w > 0 by the inlier rule, so the sum of w over them is positive and H_out keeps its sign.
+ *   keep_h_dev uint8 [n_pairs][cap]: 1 at the queries q of the inliers of Hw (the winner before step 4), 0 in every other column.
+ *   H_out_dev float64 [n_pairs][9];  sv_dev float64 [n_pairs][3].
+ *   h_info_dev int32 [n_pairs][8]: survivors m (as given), samples with a model (ok != 0), n(Hw), n_s, best sample, 0 when the refit
+ *   won else -1, 0, status bits (1: m < 5, 2: no model).
+ *
+ * thr2h is (float)(thr * thr), thr = threshold_h / ((K[0] + K[4]) / 2): VERIFY's thr2 at the homography's own threshold.
+ * Errors (SFM_ERR_ARG, before any device call): negative sizes, n_pairs * cap or n_nodes above 2^31 - 1, n_pairs above (2^31 - 1) / 1024,
+ *   n_img outside 1..65 536, budget outside 1..1024, a NaN thr2h, refit outside 0..1, NULL where the count is non-zero (img_off_dev always).
+ * ---------------------------------------------------------------------- */
+int sfm_verify_h_models(const int32_t* samp_dev, const int32_t* surv_dev, const int32_t* m_dev, const int32_t* pair_img_dev,
+                        const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes, int64_t n_pairs, int64_t cap, int budget,
+                        int32_t* ok_dev, double* Hm_dev, void* stream);
+int sfm_verify_h_score(const double* Hm_dev, const int32_t* ok_dev, const int32_t* surv_dev, const int32_t* m_dev, const int32_t* pair_img_dev,
+                       const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes, int64_t n_pairs, int64_t cap, int budget,
+                       float thr2h, int32_t* counts_dev, uint64_t* best_dev, void* stream);
+int sfm_verify_h_select(const double* Hm_dev, const int32_t* ok_dev, const uint64_t* best_dev, const int32_t* surv_dev, const int32_t* m_dev,
+                        const int32_t* pair_img_dev, const int32_t* img_off_dev, int n_img, const double* xn_dev, int64_t n_nodes,
+                        int64_t n_pairs, int64_t cap, int budget, float thr2h, int refit, uint8_t* keep_h_dev, double* H_out_dev,
+                        double* sv_dev, int32_t* h_info_dev, void* stream);
+int sfm_host_homography4(const double* x1_host, const double* x2_host, double* H_host);
+int sfm_host_verify_h_refit(const double* M81_host, double* H_host);
+int sfm_host_verify_h_normalise(const double* H_host, double* H_out_host, double* sv_host);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

@@ -148,6 +148,12 @@ SIGNATURES = {
     "sfm_verify_lo": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp, _vp, _vp]),
     "sfm_verify_lo_pick": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sfm_host_verify_refit": (_int, [_vp, _vp]),
+    "sfm_verify_h_models": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
+    "sfm_verify_h_score": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp]),
+    "sfm_verify_h_select": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _i64, _int, _f32, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_host_homography4": (_int, [_vp, _vp, _vp]),
+    "sfm_host_verify_h_refit": (_int, [_vp, _vp]),
+    "sfm_host_verify_h_normalise": (_int, [_vp, _vp, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

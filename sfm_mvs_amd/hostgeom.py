@@ -57,6 +57,35 @@ def verify_refit(M):
     return E.reshape(3, 3)
 
 
+def homography4(x1n, x2n):
+    """The four-point homography of `sfm_verify_h_models` on the host (`sfm_host_homography4`): x2 ~ H x1 with H[2, 2] = 1, (3, 3);
+    None without a model (a zero pivot of the 8 x 8 elimination or a non-finite word)."""
+    a = np.ascontiguousarray(np.asarray(x1n, np.float64).reshape(4, 2))
+    b = np.ascontiguousarray(np.asarray(x2n, np.float64).reshape(4, 2))
+    H = np.empty(9)
+    _lib.check(_lib.lib().sfm_host_homography4(a.ctypes.data_as(_vp), b.ctypes.data_as(_vp), H.ctypes.data_as(_vp)), "sfm_host_homography4")
+    return H.reshape(3, 3) if H[8] != 0 else None
+
+
+def verify_h_refit(M):
+    """The refit of `sfm_verify_h_select` (`sfm_host_verify_h_refit`): the 9 x 9 moment matrix of the inliers' DLT rows -> its smallest
+    right singular vector (3, 3), unit norm, sign as the Jacobi sweeps leave it.  The function lane 0 runs, on the host."""
+    Mc = np.ascontiguousarray(np.asarray(M, np.float64).reshape(81))
+    H = np.empty(9)
+    _lib.check(_lib.lib().sfm_host_verify_h_refit(Mc.ctypes.data_as(_vp), H.ctypes.data_as(_vp)), "sfm_host_verify_h_refit")
+    return H.reshape(3, 3)
+
+
+def verify_h_normalise(H):
+    """Step 4 of `sfm_verify_h_select` (`sfm_host_verify_h_normalise`): (H over its middle singular value (3, 3), the singular values
+    over the middle one (3,), descending)."""
+    Hc = np.ascontiguousarray(np.asarray(H, np.float64).reshape(9))
+    out, sv = np.empty(9), np.empty(3)
+    _lib.check(_lib.lib().sfm_host_verify_h_normalise(Hc.ctypes.data_as(_vp), out.ctypes.data_as(_vp), sv.ctypes.data_as(_vp)),
+               "sfm_host_verify_h_normalise")
+    return out.reshape(3, 3), sv
+
+
 def epnp(K, Xw, uv):
     """EPnP on 4..64 correspondences (`sfm_host_epnp`): R (3,3), t (3,)."""
     Kc = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))

@@ -19,6 +19,7 @@ LDS_IMAGES = 256                # SFM_REGISTER_LDS_IMAGES: above it view_scores 
 MAX_IMAGES = 4096               # register_tracks: the seed order comes from sfm_view_pair_counts, which takes no more cameras
 E_PROB, E_THRESHOLD = 0.999, 0.4   # the essential-matrix RANSAC of tracks.verify_keep
 # Defaults of register_tracks, calibrated with the CPU twin of the loop (tests/register_cases.py) on the scenes of docs/tracks.md §10.4
+CONFIG_GENERAL, CONFIG_PLANAR = 1, 2          # verify.CONFIG_GENERAL, verify.CONFIG_PLANAR
 MIN_CORR = 30                   # 2D-3D correspondences an image needs to be tried, and PnP inliers it needs to register
 MIN_SEED = 100                  # points the seed pair's model round has to leave
 BA_EVERY = 4                    # registrations between two bundle adjustments
@@ -313,11 +314,29 @@ def _camera(K, R, t):
     return K @ np.c_[np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)]
 
 
+def _pair_config(pair_config, n_pairs):
+    """The configuration words of the pairs as a list of ints, or None; SfmHipError on a wrong length or a word outside 0..3."""
+    if pair_config is None:
+        return None
+    if getattr(pair_config, "is_cuda", False):
+        raise SfmHipError("register_tracks: pair_config must be a host sequence (download `verify_pairs(...)[\"config\"]` first)")
+    try:
+        words = [int(w) for w in pair_config]
+    except (TypeError, ValueError):
+        raise SfmHipError(f"register_tracks: pair_config {pair_config!r} must be a sequence of configuration words") from None
+    if len(words) != n_pairs:
+        raise SfmHipError(f"register_tracks: pair_config holds {len(words)} words for {n_pairs} pairs")
+    if any(not 0 <= w <= 3 for w in words):
+        raise SfmHipError("register_tracks: pair_config words must be 0..3 (verify.CONFIG_NONE, _GENERAL, _PLANAR, _ROTATING)")
+    return words
+
+
 def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_seed=MIN_SEED, seed_tries=5, max_tries=2, pnp=None,
-                  ba_every=BA_EVERY, ba=None, log=None):
+                  ba_every=BA_EVERY, ba=None, log=None, pair_config=None):
     """The loop of `register_tracks` on an engine (see `_HipEngine` for what one provides).  Argument errors are raised before the engine
     does any work."""
     n_img = int(n_img)
+    config = _pair_config(pair_config, len(pairs))
     if n_img < 2:
         raise SfmHipError(f"register_tracks: {n_img} images; a seed pair needs two")
     if seed_pair is not None:
@@ -342,13 +361,17 @@ def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_s
     shared = eng.shared()
     if seed_pair is None:
         count = np.array([shared[a, b] if 0 <= a < n_img and 0 <= b < n_img and a != b else 0 for a, b in pairs], np.int64)
-        cand = [pairs[p] for p in np.argsort(-count, kind="stable") if count[p] > 0]      # most shared tracks first, ties to the lower pair index
+        cand = [p for p in np.argsort(-count, kind="stable") if count[p] > 0]             # most shared tracks first, ties to the lower pair index
+        if config is not None:                                         # GENERAL pairs in that order, then PLANAR; no baseline or no model: never a seed
+            cand = [p for p in cand if config[p] == CONFIG_GENERAL] + [p for p in cand if config[p] == CONFIG_PLANAR]
+        words = [config[p] for p in cand] if config is not None else None
+        cand = [pairs[p] for p in cand]
     else:
-        cand = [seed_pair]
+        cand, words = [seed_pair], None
     P = np.zeros((n_img, 3, 4))
     registered = np.zeros(n_img, np.uint8)
     best, rejected, model, seeds = 0, 0, None, []
-    for a, b in cand:
+    for k, (a, b) in enumerate(cand):
         if rejected >= seed_tries:
             break
         lo, hi = min(a, b), max(a, b)
@@ -363,6 +386,8 @@ def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_s
             model = eng.round(registered, P)
             points = model["points"]
         seeds.append(dict(pair=(a, b), shared=int(shared[lo, hi]), points=points))
+        if words is not None:
+            seeds[-1]["config"] = words[k]
         say(f"register: seed {(a, b)} shares {int(shared[lo, hi])} tracks, its round leaves {points} points")
         best = max(best, points)
         if pose is not None and points >= min_seed:
@@ -418,12 +443,18 @@ def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_s
 
 def register_tracks(store, n_query, pairs, keypoints, K, frame_size, ratio=0.70, keep=None, seed_pair=None, min_len=2, max_len=None, huber=1.0,
                     obs_thresh=2.0, max_reproj=2.0, min_angle_deg=2.0, refine_iters=10, grid=8, min_corr=MIN_CORR, min_seed=MIN_SEED, seed_tries=5,
-                    max_tries=2, pnp=None, ba_every=BA_EVERY, ba=None, log=None):
+                    max_tries=2, pnp=None, ba_every=BA_EVERY, ba=None, log=None, pair_config=None):
     """Cameras of unordered images from their all-pairs matches.  store, n_query, pairs as `sharded.match_pairs_sharded` returns and takes
     them; keypoints: list over images of [n_i, 2] float32 device tensors, 2 to 4 096 images (the four kernels take 65 536; the seed
     order is counted by sfm_view_pair_counts, which takes 4 096); K 3 x 3 (one camera model); frame_size (width, height).  SfmHipError
     before any device work for: min_len < 2, more than 4 096 images, a seed_pair that does not name two different images, min_corr < 4
-    (solve_pnp_ransac takes no fewer), min_seed, seed_tries or max_tries < 1, ba_every < 0.
+    (solve_pnp_ransac takes no fewer), min_seed, seed_tries or max_tries < 1, ba_every < 0, a pair_config of another length than pairs or
+    with a word outside 0..3.
+
+    pair_config: None, or a host sequence of len(pairs) two-view configuration words (`verify_pairs(homography=...)["config"]`,
+    downloaded).  With it and no explicit seed_pair the seed candidates are the GENERAL pairs in the order below, then the PLANAR pairs;
+    a ROTATING pair (no baseline) or a pair without a model is never tried, and every entry of `seeds` gains `config`.  An explicit
+    seed_pair is honoured whatever its word.
 
     Tracks are built once.  The seed is the pair with the most shared tracks (or `seed_pair`) whose essential matrix, recoverPose and
     one model round leave at least `min_seed` points; up to `seed_tries` candidates are rejected before SfmHipError.  A model round
@@ -447,9 +478,10 @@ def register_tracks(store, n_query, pairs, keypoints, K, frame_size, ratio=0.70,
     end cost one round each; a failed PnP costs none), and ONE download at the end."""
     if min_len < 2:
         raise SfmHipError(f"register_tracks: min_len {min_len} must be at least 2 (a point needs two views)")
+    _pair_config(pair_config, len(pairs))
     if len(keypoints) > MAX_IMAGES:
         raise SfmHipError(f"register_tracks: {len(keypoints)} images exceed {MAX_IMAGES}, the limit of sfm_view_pair_counts, which counts the "
                           "tracks two images share for the seed order")
     eng = _HipEngine(store, n_query, pairs, keypoints, K, frame_size, ratio, keep, min_len, max_len, huber, obs_thresh, max_reproj, min_angle_deg,
                      refine_iters, grid)
-    return register_loop(eng, len(keypoints), pairs, K, seed_pair, min_corr, min_seed, seed_tries, max_tries, pnp, ba_every, ba, log)
+    return register_loop(eng, len(keypoints), pairs, K, seed_pair, min_corr, min_seed, seed_tries, max_tries, pnp, ba_every, ba, log, pair_config)

@@ -8,7 +8,11 @@ counter-based sampler, replaces the sequential RANSAC of `ransac.find_essential_
 seed alone, and differs from the per-pair path's masks.
 
 `top_models`, `local_optimise` and `pick` are the three launches of the local optimisation ("VERIFY-LO"; docs/tracks.md §12) that
-`verify_pairs(lo=...)` puts between `score` and `select`: the best models of a pair refitted on their inliers and recounted."""
+`verify_pairs(lo=...)` puts between `score` and `select`: the best models of a pair refitted on their inliers and recounted.
+
+`h_models`, `h_score` and `h_select` are the three launches of the homography ("VERIFY-H"; docs/tracks.md §13) that
+`verify_pairs(homography=...)` runs after `select`: a second model per pair from the same survivors and samples, and with it `config`,
+the word that tells a general pair from one that sees a plane or has no baseline (`pair_config`)."""
 import ctypes
 
 import numpy as np
@@ -31,6 +35,11 @@ MAX_TOP, MAX_ROUNDS = 16, 8      # SFM_VERIFY_LO_MAX_TOP, SFM_VERIFY_LO_MAX_ROUN
 # docs/tracks.md §12.4: the setting with the smallest top * rounds whose mean recall over the nine 30 % scenes is within a point of the
 # best setting tried and whose share of planted outliers kept stays within a point of the plain path's on every (share, m) mean.
 DEFAULT_LO = dict(top=1, rounds=1, widen=(3.0,))
+CONFIG_NONE, CONFIG_GENERAL, CONFIG_PLANAR, CONFIG_ROTATING = 0, 1, 2, 3
+H_MODEL_BYTES = 80               # a sample of `verify_pairs(homography=...)`: nine float64, its flag and its count
+# docs/tracks.md §13.4: the threshold is the smallest of the grid at which keep_h recalls the planted inliers of the planar scenes no worse
+# than keep recalls those of the general scenes; min_ratio and rot_spread are the geometric means of the two sides they separate.
+DEFAULT_HOMOGRAPHY = dict(threshold=1.2, min_ratio=0.246, rot_spread=1.525, min_inliers=8, refit=1)
 
 
 def _i32(t, what, shape):
@@ -294,6 +303,120 @@ def pick(top, E_lo, n_lo, round_lo, budget, out=None):
     return E_sel, nm_sel, best_sel, lo_info
 
 
+def _h_models_args(who, Hm, ok, surv, m, pairs, img_off, xn):
+    n_pairs, cap = _surv(surv)
+    n_img, n_nodes = _n_img(img_off), _xn(xn)
+    require_cuda(Hm, ok)
+    if ok.dtype != torch.int32 or ok.dim() != 2 or ok.shape[0] != n_pairs or not ok.is_contiguous():
+        raise SfmHipError(f"{who}: ok must be a contiguous int32 [n_pairs, H] device tensor")
+    H = _budget(ok.shape[1])
+    _typed(Hm, torch.float64, (n_pairs, H, 9), "Hm")
+    _i32(m, "m", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    return n_pairs, cap, n_img, n_nodes, H
+
+
+def _thr2h(thr2h):
+    thr2h = float(thr2h)
+    if thr2h != thr2h:
+        raise SfmHipError("verify: thr2h is NaN")
+    return thr2h
+
+
+def h_models(samp, surv, m, pairs, img_off, xn, out=None):
+    """sfm_verify_h_models: the four-point homography of the first four slots of every sample of `samples`, the bits
+    `hostgeom.homography4` returns.  Returns (ok int32 [n_pairs, H], Hm float64 [n_pairs, H, 9], zero without a model).  No host wait."""
+    n_pairs, cap = _surv(surv)
+    n_img, n_nodes = _n_img(img_off), _xn(xn)
+    require_cuda(samp)
+    if samp.dtype != torch.int32 or samp.dim() != 3 or samp.shape[0] != n_pairs or samp.shape[2] != 5 or not samp.is_contiguous():
+        raise SfmHipError("h_models: samp must be a contiguous int32 [n_pairs, H, 5] device tensor")
+    H, dev = _budget(samp.shape[1]), surv.device
+    _i32(m, "m", (n_pairs,))
+    _i32(pairs, "pairs", (n_pairs, 2))
+    if out is None:
+        out = (torch.empty((n_pairs, H), dtype=torch.int32, device=dev), torch.empty((n_pairs, H, 9), dtype=torch.float64, device=dev))
+    ok, Hm = _i32(out[0], "ok", (n_pairs, H)), _typed(out[1], torch.float64, (n_pairs, H, 9), "Hm")
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_h_models(ptr(samp) if n_pairs else None, ptr(surv) if n_pairs * cap else None, ptr(m) if n_pairs else None,
+                                             ptr(pairs) if n_pairs else None, ptr(img_off), n_img, ptr(xn) if n_nodes else None, n_nodes, n_pairs,
+                                             cap, H, ptr(ok) if n_pairs else None, ptr(Hm) if n_pairs else None, stream_ptr()),
+              "sfm_verify_h_models")
+    return ok, Hm
+
+
+def h_score(Hm, ok, surv, m, pairs, img_off, xn, thr2h, out=None):
+    """sfm_verify_h_score: (counts int32 [n_pairs, H], best int64 [n_pairs] holding the uint64 key (count << 32) | (0xFFFFFFFF - s) of the
+    best sample, 0 without one) under the transfer error of x1 -> x2.  thr2h: `thr2_of(K, the homography's threshold)`.  No host wait."""
+    n_pairs, cap, n_img, n_nodes, H = _h_models_args("h_score", Hm, ok, surv, m, pairs, img_off, xn)
+    thr2h, dev = _thr2h(thr2h), surv.device
+    if out is None:
+        out = (torch.empty((n_pairs, H), dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.int64, device=dev))
+    counts, best = _i32(out[0], "counts", (n_pairs, H)), _typed(out[1], torch.int64, (n_pairs,), "best")
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_h_score(ptr(Hm) if n_pairs else None, ptr(ok) if n_pairs else None, ptr(surv) if n_pairs * cap else None,
+                                            ptr(m) if n_pairs else None, ptr(pairs) if n_pairs else None, ptr(img_off), n_img,
+                                            ptr(xn) if n_nodes else None, n_nodes, n_pairs, cap, H, thr2h, ptr(counts) if n_pairs else None,
+                                            ptr(best) if n_pairs else None, stream_ptr()), "sfm_verify_h_score")
+    return counts, best
+
+
+def h_select(Hm, ok, best, surv, m, pairs, img_off, xn, thr2h, refit=1, out=None):
+    """sfm_verify_h_select: (keep_h uint8 [n_pairs, cap], H float64 [n_pairs, 9] scaled to a middle singular value of 1, sv float64
+    [n_pairs, 3] descending with sv[:, 1] = 1, h_info int32 [n_pairs, 8]) of the best sample of every pair, refitted once on its inliers
+    when `refit` is 1 and kept only when that counts strictly more.  No host wait."""
+    n_pairs, cap, n_img, n_nodes, H = _h_models_args("h_select", Hm, ok, surv, m, pairs, img_off, xn)
+    thr2h, dev = _thr2h(thr2h), surv.device
+    if refit not in (0, 1):
+        raise SfmHipError(f"h_select: refit must be 0 or 1 (got {refit!r})")
+    _typed(best, torch.int64, (n_pairs,), "best")
+    if out is None:
+        out = (torch.empty((n_pairs, cap), dtype=torch.uint8, device=dev), torch.empty((n_pairs, 9), dtype=torch.float64, device=dev),
+               torch.empty((n_pairs, 3), dtype=torch.float64, device=dev), torch.empty((n_pairs, 8), dtype=torch.int32, device=dev))
+    keep_h, Hb, sv, h_info = out
+    _typed(keep_h, torch.uint8, (n_pairs, cap), "keep_h")
+    _typed(Hb, torch.float64, (n_pairs, 9), "H_out")
+    _typed(sv, torch.float64, (n_pairs, 3), "sv")
+    _i32(h_info, "h_info", (n_pairs, 8))
+    with on_device(dev):
+        check(_lib.lib().sfm_verify_h_select(ptr(Hm) if n_pairs else None, ptr(ok) if n_pairs else None, ptr(best) if n_pairs else None,
+                                             ptr(surv) if n_pairs * cap else None, ptr(m) if n_pairs else None, ptr(pairs) if n_pairs else None,
+                                             ptr(img_off), n_img, ptr(xn) if n_nodes else None, n_nodes, n_pairs, cap, H, thr2h, int(refit),
+                                             ptr(keep_h) if n_pairs * cap else None, ptr(Hb) if n_pairs else None, ptr(sv) if n_pairs else None,
+                                             ptr(h_info) if n_pairs else None, stream_ptr()), "sfm_verify_h_select")
+    return keep_h, Hb, sv, h_info
+
+
+def homography_settings(homography):
+    """`homography=True` or dict(threshold=, min_ratio=, rot_spread=, min_inliers=, refit=) -> the full dict, missing keys from
+    `DEFAULT_HOMOGRAPHY`; None for homography=None."""
+    if homography is None or homography is False:
+        return None
+    if homography is True:
+        homography = {}
+    if not isinstance(homography, dict) or set(homography) - set(DEFAULT_HOMOGRAPHY):
+        raise SfmHipError(f"verify: homography must be None, True or a dict of {', '.join(DEFAULT_HOMOGRAPHY)} (got {homography!r})")
+    s = dict(DEFAULT_HOMOGRAPHY, **homography)
+    try:
+        s = dict(threshold=float(s["threshold"]), min_ratio=float(s["min_ratio"]), rot_spread=float(s["rot_spread"]),
+                 min_inliers=int(s["min_inliers"]), refit=int(s["refit"]))
+    except (TypeError, ValueError) as e:
+        raise SfmHipError(f"verify: homography settings must be numbers (got {homography!r})") from e
+    if not s["threshold"] > 0 or not s["min_ratio"] >= 0 or not s["rot_spread"] >= 1 or s["min_inliers"] < 0 or s["refit"] not in (0, 1):
+        raise SfmHipError(f"verify: homography needs threshold > 0, min_ratio >= 0, rot_spread >= 1, min_inliers >= 0 and refit 0 or 1 (got {s})")
+    return s
+
+
+def pair_config(info, h_info, h_sv, settings):
+    """The two-view configuration word of every pair, int32 [n_pairs], by torch operations on the device (no host wait): NONE when the
+    essential matrix has fewer than min_inliers Sampson inliers; otherwise GENERAL when the homography explains fewer than min_ratio of
+    them; otherwise ROTATING when its singular values spread by no more than rot_spread, else PLANAR."""
+    n_E, n_H = info[:, 2].to(torch.float64), h_info[:, 2].to(torch.float64)
+    word = torch.where(h_sv[:, 0] / h_sv[:, 2] <= settings["rot_spread"], CONFIG_ROTATING, CONFIG_PLANAR)
+    word = torch.where(n_H < settings["min_ratio"] * n_E, CONFIG_GENERAL, word)
+    return torch.where(info[:, 2] < settings["min_inliers"], CONFIG_NONE, word).to(torch.int32)
+
+
 def lo_settings(lo):
     """`lo=True` or dict(top=, rounds=, widen=) -> (top, widen tuple of `rounds` multipliers of the threshold); None for lo=None."""
     if lo is None or lo is False:
@@ -319,7 +442,7 @@ def pairs_per_chunk(budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES):
 
 
 def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DEFAULT_THRESHOLD, budget=DEFAULT_BUDGET, seed=DEFAULT_SEED,
-                 max_models_bytes=MAX_MODELS_BYTES, lo=None):
+                 max_models_bytes=MAX_MODELS_BYTES, lo=None, homography=None):
     """All pairs in a fixed number of launches and no host wait.  store int32 [n_pairs, 2, cap, 2], n_query int32 [n_pairs], pairs int32
     [n_pairs, 2], img_off int32 [n_img + 1], kp float32 [n_nodes, 2]: device tensors, as `tracks.match_edges` takes them; K: 3 x 3 on the
     host.  Keypoints, survivors and samples are computed for all pairs at once (three launches); models, scores and the selection run over
@@ -333,8 +456,15 @@ def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DE
     §12) of the `top` best models of every pair, `rounds` refits each on the inliers under widen[r] * threshold; three more launches a
     chunk between `score` and `select`, which then runs on the winner alone.  The Sampson inliers of a pair (info[:, 2]) are never fewer
     than without; best sample and best model name the five-point model the winner was refitted from; the dict gains lo_info int32
-    [n_pairs, 8] (plain best count, LO count, winning candidate, its round or -1, origin sample, origin model, candidates, 0)."""
+    [n_pairs, 8] (plain best count, LO count, winning candidate, its round or -1, origin sample, origin model, candidates, 0).
+    homography: None (no further launch), True (`DEFAULT_HOMOGRAPHY`) or dict(threshold=, min_ratio=, rot_spread=, min_inliers=, refit=):
+    a homography per pair beside the essential matrix (docs/tracks.md §13), from the same survivors and the first four slots of the same
+    samples; three more launches a chunk after `select`, with or without `lo`.  keep, E, Rt and info stay the words they are without it;
+    the dict gains H float64 [n_pairs, 9] (middle singular value 1), keep_h uint8 [n_pairs, cap], h_sv float64 [n_pairs, 3], h_info int32
+    [n_pairs, 8] (survivors, samples with a model, inliers, the sample's inliers before the refit, best sample, 0 when the refit won else
+    -1, 0, status bits) and config int32 [n_pairs] (`CONFIG_NONE`, `_GENERAL`, `_PLANAR`, `_ROTATING`; `pair_config`)."""
     settings = lo_settings(lo)
+    hs = homography_settings(homography)
     thr2 = thr2_of(K, threshold)
     xn = normalise_keypoints(kp, K)
     surv, m = survivors(store, n_query, pairs, img_off, ratio)
@@ -359,6 +489,21 @@ def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DE
         E_sel = torch.empty((step, 1, SLOTS, 9), dtype=torch.float64, device=dev)
         nm_sel = torch.empty((step, 1), dtype=torch.int32, device=dev)
         best_sel = torch.empty(step, dtype=torch.int64, device=dev)
+    if hs is not None:
+        thr2h = thr2_of(K, hs["threshold"])
+        h_out = (torch.empty((n_pairs, cap), dtype=torch.uint8, device=dev), torch.empty((n_pairs, 9), dtype=torch.float64, device=dev),
+                 torch.empty((n_pairs, 3), dtype=torch.float64, device=dev), torch.empty((n_pairs, 8), dtype=torch.int32, device=dev))
+        ok_h = torch.empty((step, H), dtype=torch.int32, device=dev)
+        Hm = torch.empty((step, H, 9), dtype=torch.float64, device=dev)
+        counts_h = torch.empty((step, H), dtype=torch.int32, device=dev)
+        best_h = torch.empty(step, dtype=torch.int64, device=dev)
+
+    def homographies(a, b, part):
+        k = b - a
+        h_models(samp[a:b], *part, out=(ok_h[:k], Hm[:k]))
+        h_score(Hm[:k], ok_h[:k], *part, thr2h, out=(counts_h[:k], best_h[:k]))
+        h_select(Hm[:k], ok_h[:k], best_h[:k], *part, thr2h, hs["refit"], out=tuple(t[a:b] for t in h_out))
+
     for a in range(0, n_pairs, step):
         b = min(a + step, n_pairs)
         k = b - a
@@ -367,6 +512,8 @@ def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DE
         score(E[:k], nmodels[:k], *part, thr2, out=(counts[:k], best[:k]))
         if settings is None:
             select(E[:k], nmodels[:k], best[:k], *part, thr2, out=(keep[a:b], Eb[a:b], Rt[a:b], info[a:b]))
+            if hs is not None:
+                homographies(a, b, part)
             continue
         top_models(counts[:k], nmodels[:k], T, out=top[:k])
         local_optimise(E[:k], top[:k], *part, thr2, wide2, out=tuple(t[:k] for t in cand))
@@ -375,21 +522,28 @@ def verify_pairs(store, n_query, pairs, img_off, kp, K, ratio=0.70, threshold=DE
         # `select` saw one sample of one model: models scored, best sample and best model keep their documented meaning
         info[a:b, 1] = nmodels[:k].clamp(0, SLOTS).sum(1, dtype=torch.int32)
         info[a:b, 4:6] = lo_info[a:b, 4:6]
-    if settings is None:
-        return dict(keep=keep, E=Eb, Rt=Rt, info=info)
-    return dict(keep=keep, E=Eb, Rt=Rt, info=info, lo_info=lo_info)
+        if hs is not None:
+            homographies(a, b, part)
+    out = dict(keep=keep, E=Eb, Rt=Rt, info=info)
+    if settings is not None:
+        out["lo_info"] = lo_info
+    if hs is not None:
+        out.update(keep_h=h_out[0], H=h_out[1], h_sv=h_out[2], h_info=h_out[3], config=pair_config(info, h_out[3], h_out[2], hs))
+    return out
 
 
-def workspace_bytes(n_pairs, cap, budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES, lo=None):
+def workspace_bytes(n_pairs, cap, budget=DEFAULT_BUDGET, max_models_bytes=MAX_MODELS_BYTES, lo=None, homography=None):
     """Bytes of the intermediate tensors `verify_pairs` allocates, without xn: survivors and samples of all pairs, and the models, model
     counts, inlier counts and best keys of one chunk; with `lo`, the keys, models, counts and rounds of a chunk's candidates and its
-    one-sample models buffer as well."""
+    one-sample models buffer as well; with `homography`, the models, flags, counts (80 bytes a sample) and best keys of a chunk."""
     n_pairs, cap, H = int(n_pairs), int(cap), int(budget)
     step = min(pairs_per_chunk(H, max_models_bytes), max(n_pairs, 1))
     total = n_pairs * (cap * 8 + 4 + H * 20) + step * (H * (4 + SLOTS * 72 + SLOTS * 4) + 8)
     settings = lo_settings(lo)
     if settings is not None:
         total += step * (settings[0] * (8 + 72 + 4 + 4) + SLOTS * 72 + 4 + 8)
+    if homography_settings(homography) is not None:
+        total += step * (H * H_MODEL_BYTES + 8)
     return total
 
 
