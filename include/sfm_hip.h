@@ -1504,6 +1504,55 @@ int sfm_host_homography4(const double* x1_host, const double* x2_host, double* H
 int sfm_host_verify_h_refit(const double* M81_host, double* H_host);
 int sfm_host_verify_h_normalise(const double* H_host, double* H_out_host, double* sv_host);
 
+/* ------------------------------------------------------------------------
+ * GUIDED (no reference counterpart; csrc/guided.hip, docs/tracks.md section 14): guided matching.  The 2-NN of every query among the
+ * train keypoints inside the epipolar band of its pair's essential matrix, as a second match store in the format of the global one,
+ * and the mutual check on it.  Two launches and one clear, on the caller's stream, no host wait.  The band test is float64, correctly
+ * rounded, in the order written, no FMA, IEEE division; the distances are float32 in the oracle's order; every other output word is a
+ * minimum of an integer key, a count or a copy, so no word depends on the order in which lanes or workgroups run.
+ * tests/np_guided.py restates every output word.  pair_img, nq, img_off, xn, nodes: as VERIFY.
+ *
+ * Inputs.  E_dev float64 [n_pairs][9] (sfm_verify_select's E_out).  active_dev uint8 [n_pairs].  desc_dev float32 [n_nodes][128], the
+ * descriptors of all images concatenated in node order, 16-byte aligned.  rev_stride: the row length of rev (below).
+ *
+ * The band.  Pair p = (i, j) has queries q < qb = max(min(nq[p], cap, size of i), 0) and train keypoints t < min(size of j, rev_stride)
+ * (size of k = img_off[k + 1] - img_off[k]).  With (a1, b1) = xn[img_off[i] + q], (a2, b2) = xn[img_off[j] + t] and E = E_dev[p]:
+ *     e0 = E0 a1 + E1 b1 + E2 * 1;  e1 = E3 a1 + E4 b1 + E5 * 1;  e2 = E6 a1 + E7 b1 + E8 * 1      (left to right)
+ *     f0 = E0 a2 + E3 b2 + E6 * 1;  f1 = E1 a2 + E4 b2 + E7 * 1;  s = a2 e0 + b2 e1 + 1 * e2
+ *     (q, t) is in the band  <=>  (float)(s * s / (((e0 e0 + e1 e1) + f0 f0) + f1 f1)) <= thr2g
+ *   the words of sfm_verify_score.  A NaN quotient is out of the band, so an all-zero or non-finite E has an empty band.  The band is
+ *   empty (qb = 0) when an image is outside 0..n_img-1, when i == j and when active[p] == 0; a keypoint whose node lies outside
+ *   0..n_nodes-1 is in no band.  (The kernel decides most tests by comparing s * s with thr2g * denominator under a guard band of
+ *   2^-22 and divides inside it: the decision is the one above for every input.)
+ *
+ * The distance of (q, t) is d = sqrtf(l2sqr(desc[img_off[i] + q], desc[img_off[j] + t])) with l2sqr the direct form of A2 (the oracle's
+ * orc_l2sqr_f32 at n = 128): acc[l] (l = 0..7) starts at 0 and takes acc[l] = acc[l] + (a[8 k + l] - b[8 k + l])^2 for k = 0..15;
+ * s_l = acc[l] + acc[l + 4] (l = 0..3); l2sqr = ((s_0 + s_1) + s_2) + s_3.  A CANDIDATE is a band pair whose d is neither NaN nor +inf.
+ *
+ * sfm_guided_match — store_g_dev int32 [n_pairs][2][cap][2], the format of sfm_knn2_* blocks stacked per pair (what sfm_match_edges,
+ *   sfm_verify_survivors read).  For q < qb the two candidates with the smallest key ((uint64)bits(d) << 32) | t: trainIdx at
+ *   [p][0][q][0..1], the float32 bits of d at [p][1][q][0..1]; a missing neighbour is -1 with +inf.  Rows qb <= q < cap are (-1, -1,
+ *   +inf, +inf).  (A2's sequential strict-'<' rule restricted to the band.)  In the same pass every candidate lowers
+ *   rev[p][t] = min(((uint64)bits(d) << 32) | q).  rev is the workspace: uint64 [n_pairs][rev_stride], cleared to all ones by the call.
+ *   With thr2g = +inf, a finite E with a non-zero denominator and rev_stride >= the size of j, store_g[p] is the KNN store of the pair.
+ *
+ * sfm_guided_mutual — keep_g_dev uint8 [n_pairs][cap]: 1 <=> q < qb', trainIdx0 = t0 in 0..rev_stride-1 and (uint32)rev[p][t0] == q;
+ *   0 in every other column.  qb' is qb without the active flag (the store of an inactive pair has no neighbour).
+ *   info_g_dev int32 [n_pairs][4]: qb', queries q < qb' with trainIdx0 >= 0, with trainIdx1 >= 0, with keep_g set.
+ *
+ * sfm_guided_ws_bytes = n_pairs * rev_stride * 8 (0 for arguments sfm_guided_match rejects).
+ * Errors (SFM_ERR_ARG, before any device call): negative sizes, n_pairs, cap, rev_stride, n_pairs * cap, n_pairs * rev_stride or
+ *   n_nodes above 2^31 - 1, n_img outside 1..65 536, a NaN thr2g, a workspace smaller than sfm_guided_ws_bytes, desc_dev not 16-byte
+ *   aligned, NULL where the count is non-zero (img_off_dev always).
+ * ---------------------------------------------------------------------- */
+size_t sfm_guided_ws_bytes(int64_t n_pairs, int64_t rev_stride);
+int sfm_guided_match(const float* desc_dev, const double* xn_dev, int64_t n_nodes, const double* E_dev, const uint8_t* active_dev,
+                     const int32_t* pair_img_dev, const int32_t* nq_dev, const int32_t* img_off_dev, int n_img, int64_t n_pairs, int64_t cap,
+                     float thr2g, int32_t* store_g_dev, void* ws_dev, size_t ws_bytes, int64_t rev_stride, void* stream);
+int sfm_guided_mutual(const int32_t* store_g_dev, const void* ws_dev, size_t ws_bytes, int64_t rev_stride, const int32_t* pair_img_dev,
+                      const int32_t* nq_dev, const int32_t* img_off_dev, int n_img, int64_t n_pairs, int64_t cap, uint8_t* keep_g_dev,
+                      int32_t* info_g_dev, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

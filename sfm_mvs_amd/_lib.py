@@ -154,6 +154,9 @@ SIGNATURES = {
     "sfm_host_homography4": (_int, [_vp, _vp, _vp]),
     "sfm_host_verify_h_refit": (_int, [_vp, _vp]),
     "sfm_host_verify_h_normalise": (_int, [_vp, _vp, _vp]),
+    "sfm_guided_ws_bytes": (_sz, [_i64, _i64]),
+    "sfm_guided_match": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp, _sz, _i64, _vp]),
+    "sfm_guided_mutual": (_int, [_vp, _vp, _sz, _i64, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

@@ -8,7 +8,8 @@ form `ba.bundle_adjust_schur(cams, K, X, obs, cam_idx, pt_idx)` takes.  `refine_
 docs/tracks.md §8) refine each point under a Huber loss, flag observations one by one and keep a track with its inliers only:
 `run_tracks(robust=True)`.  `adjust_tracks` ("TRACKS-BA"; docs/tracks.md §9) bundle-adjusts what `run_tracks` returned and gives back
 the camera matrices `run_tracks` takes.  `densify_tracks` ("MVS-PLAN"; docs/mvs.md §8) plans every view's sources and depth range from
-the tracks and runs `mvs.run_mvs` with them: the frames may come in any order."""
+the tracks and runs `mvs.run_mvs` with them: the frames may come in any order.  `guided_keep` ("GUIDED"; docs/tracks.md §14) matches
+every pair again inside the epipolar band of its verified essential matrix and returns the store and mask `run_tracks` takes."""
 import numpy as np
 import torch
 
@@ -401,3 +402,31 @@ def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70, batched=False, 
         second = ops.mask_indices(mask2, nonzero=True).long()
         keep[p].index_fill_(0, out_q[:m].long()[first[second]], 1)
     return keep
+
+
+def guided_keep(descriptors, store, n_query, pairs, keypoints, K, ratio=0.70, guided_threshold=None, min_inliers=None, mutual=True,
+                max_rev_bytes=None, **kw):
+    """Guided matching as one call (docs/tracks.md §14): `verify.verify_pairs` on the global store, `guided.guided_pairs` under the
+    essential matrices it left, `verify.verify_pairs` again on the guided store.  descriptors: list over images of [n_i, 128] float32
+    device tensors; store, n_query, pairs, keypoints, K, ratio as `verify_keep` takes them; guided_threshold (pixels), min_inliers,
+    mutual, max_rev_bytes go to `guided_pairs` (None: its defaults); **kw (threshold, budget, seed, lo) to both verifications.
+    Returns (store_g int32 [n_pairs, 2, cap, 2], keep uint8 [n_pairs, cap]): keep is the second verification's mask, and the mutual
+    mask as well when `mutual`; both go to `match_edges` / `run_tracks(store_g, ..., keep=keep)` as they are.  No host wait."""
+    from . import guided, verify
+    if len(descriptors) != len(keypoints):
+        raise SfmHipError(f"guided_keep: {len(descriptors)} descriptor sets for {len(keypoints)} images")
+    require_cuda(store, *descriptors)
+    dev = store.device
+    to_dev = lambda v, shape: (v.to(device=dev, dtype=torch.int32) if isinstance(v, torch.Tensor) else _upload(np.asarray(v, np.int32), dev)).reshape(shape).contiguous()
+    sizes = [int(k.shape[0]) for k in keypoints]
+    if [int(d.shape[0]) for d in descriptors] != sizes or any(d.dim() != 2 or d.shape[1] != 128 for d in descriptors):
+        raise SfmHipError("guided_keep: descriptors must be [n_i, 128] with the n_i of the keypoints")
+    kp = torch.cat([k.to(device=dev, dtype=torch.float32).reshape(-1, 2) for k in keypoints]).contiguous()
+    desc = torch.cat([d.to(device=dev, dtype=torch.float32) for d in descriptors]).contiguous()
+    store, nq, pr, img_off = store.contiguous(), to_dev(n_query, (-1,)), to_dev(pairs, (-1, 2)), image_offsets(sizes, dev)
+    first = verify.verify_pairs(store, nq, pr, img_off, kp, K, ratio, **kw)
+    opts = {k: v for k, v in dict(threshold=guided_threshold, min_inliers=min_inliers, max_rev_bytes=max_rev_bytes).items() if v is not None}
+    g = guided.guided_pairs(desc, nq, pr, img_off, kp, K, first["E"], first["info"], mutual=mutual, cap=int(store.shape[2]),
+                            max_size=max(sizes) if sizes else 0, **opts)
+    keep = verify.verify_pairs(g["store"], nq, pr, img_off, kp, K, ratio, **kw)["keep"]
+    return g["store"], (keep & g["keep"] if mutual else keep)
