@@ -224,8 +224,9 @@ int sfm_mask_indices(const uint8_t* mask_dev, int64_t n, int mode, int32_t* idx_
  * normalise_w = 2 (rows = 4 only) is the same normalised result by a ~20x cheaper route:
  *   the smallest eigenvector of A^T A by inverse iteration (LDL^T, fp64), unit-normalised,
  *   cast and divided exactly like the faithful path — bit-identical to it on > 99.9 % of
- *   points, within 1 float32 ulp otherwise; lanes that do not converge (degenerate geometry)
- *   run the Jacobi sweeps.  The un-normalised vector (normalise_w = 0) has OpenCV's sign and
+ *   points, within 1 float32 ulp otherwise; lanes that do not converge (degenerate geometry),
+ *   or whose conditioning the normal equations cannot carry (16 sens > 2^-26 |w|, sens as in
+ *   normalise_w = 3: a baseline of 1e-4 of the depth), run the Jacobi sweeps.  The un-normalised vector (normalise_w = 0) has OpenCV's sign and
  *   is only offered by the faithful path.
  * normalise_w = 3 (rows = 4 only) is the GUARDED fast path: the result of 2 is kept only where every component of the unit
  *   vector keeps a margin of max(2^-40, 16 eps lambda1/lambda3) from the nearest float32 rounding boundary (the distance

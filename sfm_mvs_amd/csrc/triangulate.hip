@@ -162,6 +162,7 @@ __device__ __forceinline__ void dlt_build(double (&At)[4][M], const double* __re
 // path + sfm.py:54 do, the result is BIT-IDENTICAL to it on > 99.9 % of points and within 1 ulp otherwise (the two
 // vectors differ by ~1e-10 before the cast).  A lane that has not converged after kFastIters steps (a start vector
 // orthogonal to the solution, lambda3 ~ lambda4: degenerate geometry) runs the Jacobi path instead.  Returns false then.
+// (triangulate_kernel also sends the lanes there whose `sens` says the squared conditioning lost the float32 result.)
 #ifndef SFM_TRI_ITERS
 #define SFM_TRI_ITERS 12
 #endif
@@ -271,7 +272,8 @@ __device__ __forceinline__ bool dlt_nullvec_fast(const double (&At)[4][4], doubl
 // compacted so that no wave runs the slow path for a single lane.
 constexpr double kCastGuard = 9.094947017729282e-13;    // 2^-40: 300 x the rounding floor of the two vectors' difference (<= 3.5e-15 measured)
 constexpr double kSensFactor = 16.0;                    // margin = max(kCastGuard, kSensFactor * sens); measured |fast on the fused system - Jacobi on the unfused one| <= 2.0 sens (profiles/r05_tri_guard_calibration.txt)
-constexpr unsigned kRedoMark = 0x7FC0DEADu;             // quiet-NaN payload written to all four outputs of a point to redo
+constexpr double kFastWMargin = 1.4901161193847656e-08;  // 2^-26: the unguarded fast path (normalise_w = 2) keeps a lane iff kSensFactor sens <= 2^-26 |w|
+constexpr unsigned kRedoMark = 0x7FC0DEADu;            // quiet-NaN payload written to all four outputs of a point to redo
 
 __device__ __forceinline__ bool cast_margin_ok(double x, double margin) {
     const double ax = fabs(x);
@@ -373,7 +375,15 @@ __global__ __launch_bounds__(256) void triangulate_kernel(ProjPair P, const floa
     if constexpr (M == 4) {
         double sens = 0;
         // (normalise_w = 3, the guarded path, never comes here: it is triangulate_guarded_kernel + triangulate_fixup_kernel)
-        if (normalise_w == 2) have = dlt_nullvec_fast(At, Xd, &sens);
+        if (normalise_w == 2) {
+            have = dlt_nullvec_fast(At, Xd, &sens);
+            // The normal equations square the conditioning: where lambda3 - lambda4 of A^T A is small against its trace (a
+            // baseline of 1e-4 of the depth under 0.3 px of noise) the inverse-iteration vector is off by up to kSensFactor sens,
+            // i.e. X / w by 2 kSensFactor sens / |w| relative — 28 x 2^-24 measured on such a pair against the float64 SVD.  A
+            // lane keeps the fast vector only where that stays below 2^-25 (half a unit of the float32 cast), the others run the
+            // Jacobi sweeps like the lanes that did not converge.  No lane of a well-conditioned pair is affected (sens ~ 1e-13).
+            have = have && sens_factor * sens <= kFastWMargin * fabs(Xd[3]);
+        }
 #ifdef SFM_DEV_BUILD
         if (normalise_w == 4) {
             // dev calibration of the guard (scripts/dev/dev_tri_calib.py of the round-5 tree; not in release builds) on the SHIPPED configuration: the

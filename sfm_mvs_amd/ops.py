@@ -202,7 +202,8 @@ def triangulate(P1, P2, pts1, pts2, rows=4, normalise_w=False):
     argument — any strides, so the reference's transposed views of (N,2) arrays work unchanged.
     Returns X4 (4,N) float32 CUDA tensor.  normalise_w: False (raw singular vector, OpenCV's sign), True (divided by
     w in float32), "fast" (the same normalised result via inverse iteration on A^T A instead of Jacobi sweeps:
-    bit-identical on > 99.9 % of points, 1 ulp otherwise; rows = 4 only) or "guarded" (the fast path where its float32
+    bit-identical on > 99.9 % of points, 1 ulp otherwise — lanes that do not converge or are too ill-conditioned for the
+    normal equations run the Jacobi sweeps; rows = 4 only) or "guarded" (the fast path where its float32
     casts equal the faithful path's under an EMPIRICAL bound (|fast - Jacobi| <= 2.5 sens measured on 4e6 points, guard at 16 sens; bench.py and tests/test_gpu_geometry.py bit-compare against normalise_w = 1), the Jacobi sweeps — compacted — for the ~2 % of points near a rounding
     boundary: bit-identical to True, ~8x faster; what the driver uses).
     """

@@ -378,8 +378,10 @@ def test_triangulation_one_million_distinct_points_vs_oracle(hip, oracle):
     P2n[:, 3] += P[1][:, :3] @ np.array([1e-3, 0.0, 0.0])
     xb = (P2n @ Xh)
     xb = ((xb[:2] / xb[2]).T + rng.normal(0, 0.3, (n, 2))).astype(np.float32)
-    m = 300_000          # (>= 2^18: the first pass keeps a compact reject list; here nearly every point is rejected, the per-workgroup
-                         #  queues overflow and the second pass falls back to scanning the marks)
+    m = 300_000          # (>= 2^18: the first pass keeps a compact reject list; here nearly every point is rejected, the GLOBAL list
+                         #  (cap = m / 8) overflows and the second pass falls back to scanning the marks.  The per-workgroup queues
+                         #  cannot overflow here: 1172 workgroups, one point per lane, at most 256 rejects against kQ = 1024 —
+                         #  that branch is held by test_gpu_tri_paths.py::test_reject_plans[wg_overflow])
     a2, b2 = cu(xs[0][:m]).t(), cu(xb[:m]).t()
     assert np.array_equal(hip.triangulate(P[1], P2n, a2, b2, normalise_w="guarded").cpu().numpy().view(np.uint32),
                           hip.triangulate(P[1], P2n, a2, b2, normalise_w=True).cpu().numpy().view(np.uint32))
