@@ -1554,6 +1554,75 @@ int sfm_guided_mutual(const int32_t* store_g_dev, const void* ws_dev, size_t ws_
                       const int32_t* nq_dev, const int32_t* img_off_dev, int n_img, int64_t n_pairs, int64_t cap, uint8_t* keep_g_dev,
                       int32_t* info_g_dev, void* stream);
 
+/* ------------------------------------------------------------------------
+ * RETRIEVAL (no reference counterpart; csrc/retrieval.hip, docs/retrieval.md): image retrieval.  One VLAD signature per image from the
+ * descriptors of its keypoints and a vocabulary of centres, the k most similar images of every image, and the pair list of those
+ * neighbourhoods: what every consumer of a pair list takes in place of all_pairs when the images have no order.  Every integer
+ * output is a sum, a minimum, a count, a rank or a copy; every float output is an elementwise, correctly rounded function of
+ * integers, in the order written (no FMA, IEEE / and sqrt), so no word depends on the order in which lanes or workgroups run.
+ * Every loop is bounded in the code.  All launches go to the caller's stream, no host wait.  tests/np_retrieval.py restates every
+ * output word.  Nodes, img_off, n_img (1..65 536): as TRACKS; a node at or past img_off[n_img - 1] belongs to the last image.
+ * desc_dev float32 [n_nodes][128], 16-byte aligned, as GUIDED.  centres_dev float32 [C][128], 1 <= C <= 256, 16-byte aligned.
+ *
+ * sfm_vlad_accumulate — assignment and sums in one entry point (one clear and two launches).
+ *   distance    for node u and centre c, d2 = l2sqr(desc[u], centre[c]), the direct form of GUIDED: acc[l] (l = 0..7) starts at 0 and
+ *               takes acc[l] = acc[l] + (a[8 k + l] - b[8 k + l])^2 for k = 0..15; s_l = acc[l] + acc[l + 4] (l = 0..3);
+ *               l2sqr = ((s_0 + s_1) + s_2) + s_3.  No square root.  A CANDIDATE is a c whose d2 is neither NaN nor +inf.
+ *   assign_dev  int32 [n_nodes]: the candidate with the smallest key ((uint64)bits(d2) << 32) | c; -1 when there is none.
+ *   term        for an assigned node of image i, r = desc[u][k] - centre[c][k] in float32 and
+ *               t = (int64) rintf(fminf(fmaxf(r * scale, -2^30), 2^30)); rintf rounds half to even.  scale: positive, finite.
+ *   acc_dev     int64 [n_img][C][128]: acc[i][c][k] = the sum of t.   count_dev int32 [n_img][C]: the assigned nodes.  The call
+ *               clears both.  A workgroup owns 1 024 consecutive nodes, cuts them at the image boundaries, sorts a segment by
+ *               centre in LDS; eight groups of 32 lanes each walk an eighth of the sorted list and sum in int64 registers while
+ *               the centre stays: one 64-bit integer atomic add per (segment, centre, dimension, lane group whose eighth holds
+ *               that centre) with a non-zero sum, so at most eight per (segment, centre, dimension).  DEVIATION from "the
+ *               descriptors are read once": they are read from global memory TWICE, by the assignment and again by the sums,
+ *               which must know the centre before they can form a residual; whether the second read is served by a cache has not
+ *               been measured, and the byte floor of scripts/bench_retrieval.py counts both reads.  The centres pass through LDS
+ *               32 at a time for the distances and are read from global memory, one row per run of equal centres, for the sums.
+ *
+ * sfm_vlad_centres — one Lloyd update from an accumulate call made with ONE image (img_off = [0, N]): with count[c] != 0
+ *   centre'[c][k] = (float)((double)centre[c][k] + (double)acc[c][k] / ((double)count[c] * (double)scale)); a centre with count 0 keeps
+ *   its bits.  centres_out_dev may be centres_dev.
+ *
+ * sfm_vlad_signature — per (image i, centre c), in float64: a_k = (double)acc[i][c][k] (round to nearest even above 2^53); with
+ *   ssr != 0, a_k = copysign(sqrt(|a_k|), a_k).  n2 = the sum of a_k * a_k for k = 0, 1, .. 127, left to right from 0.
+ *   q[i][c][k] = (int8) fmin(fmax(rint((a_k / sqrt(n2)) * qs), -127), 127); the block is all zero when n2 is 0 or not finite.
+ *   sig_dev int8 [n_img][C * 128].  norm2_dev int32 [n_img]: the sum of q * q over the image, at most 256 * 128 * 127^2 < 2^31; the
+ *   call clears it.  qs: float64, positive and finite (127 unless the caller knows better).
+ *
+ * sfm_vlad_shortlist — n_img <= 16 384 HERE (the similarities of all pairs pass through the workspace: n_img^2 words).
+ *   S[i][j]     the int32 sum of sig[i][.] * sig[j][.] over C * 128 bytes, exact (v_mfma_i32_16x16x64_i8; |S| <= the bound above).
+ *   sim[i][j]   (float)((double)S / sqrt((double)norm2[i] * (double)norm2[j])).
+ *   candidate   j != i with norm2[i] != 0, norm2[j] != 0 and sim[i][j] >= min_sim (float32; -inf admits all, +inf none).
+ *   nbr_dev     int32 [n_img][k]: the candidates of i in descending sim, ties to the smaller j; -1 where there are fewer than k.
+ *   nbr_sim_dev float32 [n_img][k]: their sim, -inf where missing.   1 <= k <= 64.
+ *   The workspace holds one word per (i, j); sfm_vlad_shortlist_ws_bytes(n_img) = n_img^2 * 4 (0 for an n_img outside 1..16 384).
+ *
+ * sfm_vlad_pairs — n_img <= 16 384 (an adjacency bitmap of n_img^2 bits in the workspace).  A VALID entry of nbr_dev [n_img][k] is
+ *   a j in 0..n_img-1 other than its row.  The pair (a, b), a < b, is SELECTED iff b is a valid entry of row a OR a is one of row b;
+ *   with mutual != 0: AND.  pairs_out_dev int32 [cap_pairs][2]: the selected pairs in ascending (a, b) order, those that fit.
+ *   count_dev int32 [2] = (selected, written = min(selected, cap_pairs)).  Nothing at or past the written rows is written;
+ *   cap_pairs < selected is no error.  sfm_vlad_pairs_ws_bytes(n_img): the bitmap and n_img counters, each rounded up to 256 bytes.
+ *
+ * Errors (SFM_ERR_ARG, before any device call): negative sizes, n_nodes or cap_pairs above 2^31 - 1, C outside 1..256, k outside
+ *   1..64, n_img outside 1..65 536 (accumulate, signature) or 1..16 384 (shortlist, pairs), a scale or qs that is NaN, not positive or
+ *   infinite, a NaN min_sim, a workspace smaller than the _ws_bytes twin says, desc_dev, centres_dev (accumulate) or sig_dev (shortlist)
+ *   not 16-byte aligned, NULL where the count is non-zero (everything but desc_dev, assign_dev at n_nodes = 0 and pairs_out_dev at
+ *   cap_pairs = 0).
+ * ---------------------------------------------------------------------- */
+int sfm_vlad_accumulate(const float* desc_dev, int64_t n_nodes, const float* centres_dev, int n_centres, const int32_t* img_off_dev, int n_img,
+                        float scale, int32_t* assign_dev, int64_t* acc_dev, int32_t* count_dev, void* stream);
+int sfm_vlad_centres(const float* centres_dev, const int64_t* acc_dev, const int32_t* count_dev, int n_centres, float scale,
+                     float* centres_out_dev, void* stream);
+int sfm_vlad_signature(const int64_t* acc_dev, int n_img, int n_centres, int ssr, double qs, int8_t* sig_dev, int32_t* norm2_dev, void* stream);
+size_t sfm_vlad_shortlist_ws_bytes(int n_img);
+int sfm_vlad_shortlist(const int8_t* sig_dev, const int32_t* norm2_dev, int n_img, int n_centres, int k, float min_sim, int32_t* nbr_dev,
+                       float* nbr_sim_dev, void* ws_dev, size_t ws_bytes, void* stream);
+size_t sfm_vlad_pairs_ws_bytes(int n_img);
+int sfm_vlad_pairs(const int32_t* nbr_dev, int n_img, int k, int mutual, int32_t* pairs_out_dev, int64_t cap_pairs, int32_t* count_dev,
+                   void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Dev diagnostics: when non-NULL, every knn filter workgroup b writes int64[4] =
  * {start tick, end tick (100 MHz), HW_ID, XCC_ID} at dev_buf[4*b..] and every refine workgroup w
  * int64[16] phase ticks at dev_buf[16384 + 16*w..]; NULL disables. */

@@ -157,6 +157,13 @@ SIGNATURES = {
     "sfm_guided_ws_bytes": (_sz, [_i64, _i64]),
     "sfm_guided_match": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _vp, _vp, _sz, _i64, _vp]),
     "sfm_guided_mutual": (_int, [_vp, _vp, _sz, _i64, _vp, _vp, _vp, _int, _i64, _i64, _vp, _vp, _vp]),
+    "sfm_vlad_accumulate": (_int, [_vp, _i64, _vp, _int, _vp, _int, _f32, _vp, _vp, _vp, _vp]),
+    "sfm_vlad_centres": (_int, [_vp, _vp, _vp, _int, _f32, _vp, _vp]),
+    "sfm_vlad_signature": (_int, [_vp, _int, _int, _int, _f64, _vp, _vp, _vp]),
+    "sfm_vlad_shortlist_ws_bytes": (_sz, [_int]),
+    "sfm_vlad_shortlist": (_int, [_vp, _vp, _int, _int, _int, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_vlad_pairs_ws_bytes": (_sz, [_int]),
+    "sfm_vlad_pairs": (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _vp, _sz, _vp]),
     "sfm_profile_enable": (_int, [_int]),
     "sfm_host_sync_count": (_i64, []),
     "sfm_pnp_profile_read": (_int, [_c.POINTER(_f64), _int]),

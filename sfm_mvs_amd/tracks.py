@@ -9,7 +9,8 @@ docs/tracks.md §8) refine each point under a Huber loss, flag observations one 
 `run_tracks(robust=True)`.  `adjust_tracks` ("TRACKS-BA"; docs/tracks.md §9) bundle-adjusts what `run_tracks` returned and gives back
 the camera matrices `run_tracks` takes.  `densify_tracks` ("MVS-PLAN"; docs/mvs.md §8) plans every view's sources and depth range from
 the tracks and runs `mvs.run_mvs` with them: the frames may come in any order.  `guided_keep` ("GUIDED"; docs/tracks.md §14) matches
-every pair again inside the epipolar band of its verified essential matrix and returns the store and mask `run_tracks` takes."""
+every pair again inside the epipolar band of its verified essential matrix and returns the store and mask `run_tracks` takes.
+`retrieval_pairs` ("RETRIEVAL"; docs/retrieval.md) is the pair list of images without an order: every image with its k most similar."""
 import numpy as np
 import torch
 
@@ -430,3 +431,12 @@ def guided_keep(descriptors, store, n_query, pairs, keypoints, K, ratio=0.70, gu
                             max_size=max(sizes) if sizes else 0, **opts)
     keep = verify.verify_pairs(g["store"], nq, pr, img_off, kp, K, ratio, **kw)["keep"]
     return g["store"], (keep & g["keep"] if mutual else keep)
+
+
+def retrieval_pairs(descriptors, k=8, **kw):
+    """The shortlist of pairs for images without an order (docs/retrieval.md): `retrieval.select_pairs` on the list over images of
+    [n_i, 128] float32 device tensors `guided_keep` takes; **kw (centres, n_centres, iters, seed, ssr, mutual, min_sim, value_range)
+    goes to it.  Returns the host list of (i, j), i < j, ascending: the `pairs` of `sharded.match_pairs_sharded(descriptors, pairs)`
+    and of everything after it.  One host wait."""
+    from . import retrieval
+    return retrieval.select_pairs(descriptors, None, k, **kw)[0]
