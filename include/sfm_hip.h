@@ -32,7 +32,7 @@ extern "C" {
 #define SFM_ABI_VERSION 3   /* 3 (round 6): + sfm_host_poll_count, sfm_debug_pnp_sweep_server; sfm_build_id() names every source file;
                                later, backward-compatible additions: sfm_mvs_plane_sweep, sfm_mvs_consistency; sfm_tsdf_integrate,
                                sfm_mesh_count(_ws_bytes), sfm_mesh_extract(_ws_bytes); sfm_mvs_cost_shift, sfm_mvs_cost_aggregate,
-                               sfm_mvs_cost_depth */
+                               sfm_mvs_cost_depth; sfm_mvs_patchmatch */
 
 #define SFM_OK             0
 #define SFM_ERR_ARG       -1   /* null pointer, negative size, unsupported dim, misaligned pointer/stride */
@@ -628,6 +628,59 @@ int sfm_mvs_cost_aggregate(const uint16_t* q_dev, int64_t w, int64_t h, int ndep
                            void* stream);
 int sfm_mvs_cost_depth(const uint16_t* s_dev, const uint16_t* q_dev, const float* invd_dev, int64_t w, int64_t h, int ndepth, int gate,
                        float* depth_dev, float* cost_dev, int32_t* plane_dev, void* stream);
+
+/* ------------------------------------------------------------------------
+ * MVS-PATCHMATCH  refinement of a depth map over slanted support planes (opt-in; no reference counterpart; csrc/mvs_patchmatch.hip)
+ *
+ * One entry point between sfm_mvs_plane_sweep (or sfm_mvs_cost_depth) and sfm_mvs_consistency (sfm_mvs_amd/mvs.py
+ * `patchmatch_refine`, docs/mvs.md §9).  In the reference camera the inverse depth of a plane is affine in the pixel, so a slanted
+ * matching window needs only a per-sample inverse depth; the warp of "MVS" is unchanged.  As in "MVS", every step is a correctly
+ * rounded float32 operation in the order written here (no FMA, IEEE `/` and sqrtf), and tests/np_mvs_patchmatch.py restates every
+ * output bit for bit.  Integer-to-float conversions below are exact ((float) of a small integer).
+ *
+ * sfm_mvs_patchmatch — enqueues 1 + 2*iters + 1 launches on the stream (init; per iteration a red then a black half-sweep; finish).
+ *   ref_dev, src_dev, mv_host, nsrc, w, h, radius, topk, var_min, cost_max: as sfm_mvs_plane_sweep (r 1..4, nsrc 1..8, 2r+1 <= w, h <= 32767)
+ *   qmin, qmax   0 < qmin <= qmax < inf: the admissible inverse depths of a plane at its pixel
+ *   state_dev    [h][w][4] float32 (q0, a, b, cost) per pixel, 16-byte aligned, caller-owned; written by every launch, final on return
+ *   plane        the plane (q0, a, b) of the pixel (x, y) has inverse depth q = (q0 + a*(float)(u-x)) + b*(float)(v-y) at sample (u, v)
+ *   cost         C(x, y; q0, a, b): sfm_mvs_plane_sweep's C_j at (x, y) with invd[j] replaced, per window sample (u, v), by that q:
+ *                h_i = ((M_i0*u + M_i1*v) + M_i2) + v_i*q, validity, bilinear value, the moments' order, var_min, the clamp to [0, 2],
+ *                the top-k mean and the cost 2 where the reference window leaves the frame are all as written under "MVS".
+ *                With a = b = 0 and q0 = invd[j] it is the sweep's volume word (q0 + 0 + 0 = q0).
+ *   hash         U(pix, it, c): x = seed ^ (pix*0x9E3779B9u + it*0x85EBCA6Bu + c*0xC2B2AE35u) in wrapping uint32, pix = y*w + x;
+ *                x ^= x>>16; x *= 0x7feb352du; x ^= x>>15; x *= 0x846ca68bu; x ^= x>>16;  U = (float)(int32_t)x * 0x1p-31f
+ *                (the conversion rounds to nearest even; -1 <= U <= 1).  No state: a word of (seed, pixel, iteration, draw index).
+ *   init         d = depth_init_dev[y][x] (depth_init_dev may be NULL: every pixel is hashed).  If d > 0 and qmin <= 1/d <= qmax:
+ *                q0 = 1/d; else q0 = qmin + (qmax-qmin)*(0.5f*U(pix, 0, 0) + 0.5f).  a = b = 0, cost = C(x, y; q0, 0, 0).
+ *                (A NaN, zero, negative or infinite d fails one of the comparisons.)
+ *   half-sweep   iteration it = 0..iters-1, colour 0 (red: (x+y) even) then colour 1 (black: (x+y) odd).  Every pixel of the colour
+ *                tries its candidates in this order; a candidate (q0', a', b') is evaluated only if it is admissible, and replaces
+ *                the pixel's state (with cost = its C) only if its C is strictly smaller than the state's cost:
+ *                1. for (dx, dy) = (-1,0), (1,0), (0,-1), (0,1), and if far != 0 then (-3,0), (3,0), (0,-3), (0,3): the neighbour
+ *                   (xn, yn) = (x+dx, y+dy), skipped outside the frame, with state (qn, an, bn, .):
+ *                   q0' = (qn + an*(float)(x-xn)) + bn*(float)(y-yn), a' = an, b' = bn
+ *                2. with ds = depth_step*s, ss = slope_step*s, s = 2^-it (both products exact), U_c = U(pix, it, c), and (q0, a, b)
+ *                   the state as it stands when the candidate is formed:
+ *                   depth:  (q0*(1 + ds*U_1), a, b)
+ *                   slopes: (q0, a + (ss*q0)*U_2, b + (ss*q0)*U_3)
+ *                   both:   (q0*(1 + ds*U_4), a + (ss*q0)*U_5, b + (ss*q0)*U_6)
+ *                admissible: q0', a', b' finite, qmin <= q0' <= qmax, (float)r*(fabsf(a') + fabsf(b')) <= 0.5f*q0'
+ *                (so every sample's q is >= q0'/2 > 0).  Every neighbour has the other colour (odd Manhattan distance) and a
+ *                half-sweep writes its own colour only: no word depends on the order of execution, and the update is in place.
+ *   finish       depth_dev [h][w] float32 1/q0, 0 where the reference window leaves the frame or !(cost < cost_max);
+ *                cost_dev [h][w] float32 the state's cost;
+ *                normal_dev optional [h][w][3] float32 (NULL: not written, nmat_host not read): with A = a, B = b,
+ *                C = (q0 - a*(float)x) - b*(float)y:  n_i = (N_i0*A + N_i1*B) + N_i2*C, divided by sqrtf((n_0*n_0 + n_1*n_1) + n_2*n_2);
+ *                (0, 0, 0) where the depth is 0
+ *   nmat_host    host float32 [9] N (3x3 row-major) = -R^T K^T of the reference camera, formed in float64 and cast once: the plane is
+ *                (A, B, C).K X_c = 1 in camera coordinates, so N (A, B, C) is its world normal turned towards the camera
+ *   iters 0..16 (0: init and finish only); depth_step, slope_step finite and >= 0; seed any uint32; far any int.
+ * No workspace, no atomics, no host wait.
+ * ---------------------------------------------------------------------- */
+int sfm_mvs_patchmatch(const uint8_t* ref_dev, const uint8_t* const* src_dev, const float* mv_host, int nsrc, int64_t w, int64_t h,
+                       float qmin, float qmax, int radius, int topk, float var_min, float cost_max, const float* depth_init_dev,
+                       int iters, int far, float depth_step, float slope_step, uint32_t seed, const float* nmat_host,
+                       float* state_dev, float* depth_dev, float* cost_dev, float* normal_dev, void* stream);
 
 /* ------------------------------------------------------------------------
  * MESH a surface from the MVS depth maps     after sfm.py:298 (`densify`)

@@ -269,6 +269,86 @@ P1 = 10             # a change of one plane between neighbouring pixels
 P2 = 102            # any larger change
 
 
+# Defaults of the opt-in PatchMatch refinement (run_mvs(refine=True)), chosen on the CPU model (tests/np_mvs_patchmatch.py) over the
+# grid of scripts/calibrate_mvs_patchmatch.py (tests/golden/mvs_patchmatch_calibration.json; docs/mvs.md §9)
+PM_ITERS = 3        # red-black iterations (two half-sweeps each)
+PM_DEPTH_STEP = 0.05  # relative perturbation of the inverse depth at iteration 0, halved every iteration
+PM_FAR = True       # also propagate from the neighbours at distance 3
+
+
+def normal_matrix(K, P_ref):
+    """float32 [9] N = -R^T K^T (float64, cast once): N (A, B, C) is the world normal, towards the camera, of the plane whose inverse
+    depth in the reference camera is A x + B y + C."""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    R, _ = _rt(K, P_ref)
+    return (-(R.T @ K.T)).ravel().astype(np.float32)
+
+
+def patchmatch_refine(ref, srcs, mv, qmin, qmax, depth_init=None, K=None, P_ref=None, radius=3, topk=2, var_min=None, cost_max=None,
+                      iters=PM_ITERS, far=PM_FAR, depth_step=PM_DEPTH_STEP, slope_step=None, seed=0, normals=True):
+    """PatchMatch refinement of a depth map over slanted support planes (sfm_mvs_patchmatch; docs/mvs.md §9).
+    ref, srcs, mv, radius, topk, var_min, cost_max: as plane_sweep; qmin, qmax: the admissible inverse depths (the sweep's first and
+    last plane); depth_init: an [H, W] float32 device depth map to start from (None: a hashed start at every pixel).
+    slope_step None means 1 / K[0, 0]: a relative slope of one unit of tan per focal length (K is then required); normals=True needs
+    K and P_ref.  1 + 2*iters + 1 launches on the current stream, no host wait.
+    Returns (depth [H, W] float32, cost [H, W] float32, normals [H, W, 3] float32 unit world normals facing the camera or None,
+    state [H, W, 4] float32 (q0, a, b, cost))."""
+    var_min = VAR_MIN if var_min is None else var_min
+    cost_max = COST_MAX if cost_max is None else cost_max
+    require_cuda(ref, depth_init, *srcs)
+    ref = _gray(ref)
+    srcs = [_gray(s) for s in srcs]
+    h, w = ref.shape
+    dev = ref.device
+    if any(s.shape != ref.shape or s.device != dev for s in srcs):
+        raise SfmHipError("patchmatch_refine: every source frame must have the reference's size and device")
+    mv = np.ascontiguousarray(np.asarray(mv, np.float32).reshape(-1, 12))
+    if len(mv) != len(srcs):
+        raise SfmHipError(f"patchmatch_refine: {len(srcs)} sources but {len(mv)} matrices")
+    if depth_init is not None:
+        if depth_init.dtype != torch.float32 or depth_init.shape != ref.shape or depth_init.device != dev:
+            raise SfmHipError("patchmatch_refine: depth_init must be an [H, W] float32 tensor on the reference's device")
+        depth_init = depth_init.contiguous()
+    if slope_step is None:
+        if K is None:
+            raise SfmHipError("patchmatch_refine: slope_step=None means 1 / K[0, 0]: pass K or a slope_step")
+        slope_step = 1.0 / float(np.asarray(K, np.float64).reshape(3, 3)[0, 0])
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 32:
+        raise SfmHipError(f"patchmatch_refine: seed must be a uint32 (got {seed})")
+    nmat = None
+    if normals:
+        if K is None or P_ref is None:
+            raise SfmHipError("patchmatch_refine: normals=True needs K and P_ref")
+        nmat = normal_matrix(K, P_ref)
+    state = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+    depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+    cost = torch.empty((h, w), dtype=torch.float32, device=dev)
+    nrm = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if normals else None
+    src_ptrs = (ctypes.c_void_p * max(len(srcs), 1))(*[s.data_ptr() for s in srcs])
+    with on_device(dev):
+        check(_lib.lib().sfm_mvs_patchmatch(ptr(ref), src_ptrs, mv.ctypes.data_as(ctypes.c_void_p), len(srcs), w, h, float(qmin), float(qmax),
+                                            int(radius), int(topk), float(var_min), float(cost_max), ptr(depth_init), int(iters),
+                                            1 if far else 0, float(depth_step), float(slope_step), seed,
+                                            None if nmat is None else nmat.ctypes.data_as(ctypes.c_void_p), ptr(state), ptr(depth), ptr(cost),
+                                            ptr(nrm), stream_ptr()), "sfm_mvs_patchmatch")
+    return depth, cost, nrm, state
+
+
+_REFINE_KEYS = ("iters", "far", "depth_step", "slope_step", "seed")
+
+
+def _checked_refine(refine):
+    """run_mvs's `refine` keyword as the dict of patchmatch_refine's keywords (None: no refinement), or an SfmHipError."""
+    if refine is None or refine is False:
+        return None
+    if refine is True:
+        return {}
+    if not isinstance(refine, dict) or any(k not in _REFINE_KEYS for k in refine):
+        raise SfmHipError(f"run_mvs: refine must be None, True or a dict with keys among {_REFINE_KEYS}")
+    return dict(refine)
+
+
 def _checked_neighbours(nbrs, n):
     """run_mvs's `neighbours` keyword as a list of lists of ints, or an SfmHipError: one list per view, at most MAX_VIEWS entries, each
     an index in 0..n-1 other than the view's own."""
@@ -302,7 +382,7 @@ def _checked_ranges(ranges, n, ndepth):
 
 
 def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_min=VAR_MIN, cost_max=COST_MAX, tau=0.01,
-            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8, neighbours=None, ranges=None):
+            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8, neighbours=None, ranges=None, refine=None):
     """Dense reconstruction of a registered sequence: a plane-sweep depth map per view, geometric-consistency filtering, and one
     coloured cloud.
 
@@ -322,6 +402,10 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
              contributes no point.
     ranges:  None, or per view (dmin, dmax) of its planes instead of depth_range(Xtot, P_i) (Xtot is then not read).
              Both are validated before any launch.
+    refine:  None, True or a dict of patchmatch_refine's iters / far / depth_step / slope_step / seed: every view's depth map (the
+             winner-take-all one, or the aggregated one) is refined over slanted planes before the consistency pass, with the view's
+             own sources and plane range (docs/mvs.md §9).  The result gains "normal_maps" (per view (H, W, 3) float32 device tensor:
+             unit world normals facing the camera, 0 where there is no depth) and "normals" (m, 3) float64, the points' normals.
     Returns dict(depths [per view (H, W) float32 device tensor], points (m, 3) float64, colors (m, 3) float64 B G R): shaped as
     Xtot / colorstot, so that pipeline.to_ply(path, points, colors, densify=True) writes Point_Cloud/dense.ply.
     One host wait per call: the fused point count (then one download of the points and colours); every upload is stream-ordered
@@ -339,6 +423,7 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     topk = min(int(topk), nsrc)
     nbrs = [_sequence_neighbours(i, n, nsrc) for i in range(n)] if neighbours is None else _checked_neighbours(neighbours, n)
     planes = None if ranges is None else _checked_ranges(ranges, n, ndepth)
+    refine = _checked_refine(refine)
     dev = torch.device("cuda", torch.cuda.current_device())
     if all(torch.is_tensor(im) and im.is_cuda for im in images):
         frames = [im.to(dev).contiguous() for im in images]
@@ -352,8 +437,10 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     h, w = frames[0].shape[:2]
     grays = [bgr2gray(f) for f in frames]
     # every view's planes in one upload, before the first launch (a per-view upload would wait for the previous view's sweep)
-    invd = _upload(np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)]) if planes is None else planes, dev)
-    depths = []
+    if planes is None:
+        planes = np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)])
+    invd = _upload(planes, dev)
+    depths, normal_maps = [], []
     if aggregate:
         vol = torch.empty((int(ndepth), h, w), dtype=torch.float32, device=dev)
         qbuf = torch.empty((int(ndepth), h, w), dtype=torch.uint16, device=dev)
@@ -361,6 +448,8 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     for i in range(n):
         if not nbrs[i]:                                         # no source: no sweep, an all-zero map
             depths.append(torch.zeros((h, w), dtype=torch.float32, device=dev))
+            if refine is not None:
+                normal_maps.append(torch.zeros((h, w, 3), dtype=torch.float32, device=dev))
             continue
         mv = sweep_matrices(K, Ps[i], Ps[nbrs[i]])
         if aggregate:
@@ -368,6 +457,10 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
             d, _, _ = aggregate_depth(vol, invd[i], radius if shift is None else shift, p1, p2, ndir, cost_max, q_out=qbuf, s_out=sbuf)
         else:
             d, _, _, _ = plane_sweep(grays[i], [grays[v] for v in nbrs[i]], mv, invd[i], radius, min(topk, len(nbrs[i])), var_min, cost_max)
+        if refine is not None:
+            d, _, nm, _ = patchmatch_refine(grays[i], [grays[v] for v in nbrs[i]], mv, planes[i, 0], planes[i, -1], d, K, Ps[i], radius,
+                                            min(topk, len(nbrs[i])), var_min, cost_max, **refine)
+            normal_maps.append(nm)
         depths.append(d)
     masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
@@ -379,5 +472,11 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
         consistency(depths[i], [depths[v] for v in nbrs[i]], nbrs[i], ab, i, bc, tau, min(int(min_consistent), len(nbrs[i])), unique,
                     mask_out=masks[i], xyz_out=xyz[i])
     idx = ops.mask_indices(masks).long()                       # the one host wait: the count sizes the result
-    both = torch.cat([xyz.reshape(-1, 3)[idx].double(), torch.stack(frames).reshape(-1, 3)[idx].double()], 1).cpu().numpy()
-    return dict(depths=depths, points=np.ascontiguousarray(both[:, :3]), colors=np.ascontiguousarray(both[:, 3:]))
+    cols = [xyz.reshape(-1, 3)[idx].double(), torch.stack(frames).reshape(-1, 3)[idx].double()]
+    if refine is not None:
+        cols.append(torch.stack(normal_maps).reshape(-1, 3)[idx].double())
+    both = torch.cat(cols, 1).cpu().numpy()
+    out = dict(depths=depths, points=np.ascontiguousarray(both[:, :3]), colors=np.ascontiguousarray(both[:, 3:6]))
+    if refine is not None:
+        out.update(normal_maps=normal_maps, normals=np.ascontiguousarray(both[:, 6:]))
+    return out
