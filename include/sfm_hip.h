@@ -683,6 +683,60 @@ int sfm_mvs_patchmatch(const uint8_t* ref_dev, const uint8_t* const* src_dev, co
                        float* state_dev, float* depth_dev, float* cost_dev, float* normal_dev, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MVS-FUSE  merging fusion of the depth maps of all views: averaged oriented points, a normal check (opt-in; no reference
+ *           counterpart; csrc/mvs_fuse.hip)
+ *
+ * One entry point in the place of the per-view sfm_mvs_consistency calls (sfm_mvs_amd/mvs.py `fuse`, `run_mvs(fuse=...)`,
+ * docs/mvs.md §10).  Where the filter emits a kept pixel's own sample, this merges it with the samples of its consistent neighbours:
+ * position, normal and colour averaged, and a neighbour whose normal disagrees is not consistent.  As in "MVS", every float step is a
+ * correctly rounded float32 operation in the order written here (no FMA, IEEE `/` and sqrtf), neighbours strictly in table order, and
+ * tests/np_mvs_fuse.py restates every output bit for bit.  All element offsets are 64-bit.
+ *
+ * sfm_mvs_fuse — one launch over all views: a workgroup per 16 x 16 tile and view, a lane per pixel.
+ *   depth_dev   [n][h][w] float32 depth maps of all views, stacked (0 = no depth)
+ *   normal_dev  [n][h][w][3] float32 world normals, or NULL (then normal_out_dev must be NULL too)
+ *   bgr_dev     [n][h][w][3] uint8 frames, or NULL (then bgr_out_dev must be NULL too)
+ *   table_dev   DEVICE array of n records of 512 bytes (128 32-bit words), view i at byte 512*i, holding view indices only, never an
+ *               address:
+ *                 word 0          int32   nnbr             the kernel uses min(nnbr, 8); <= 0: no neighbour
+ *                 word 1          int32   min_consistent
+ *                 words 2..9      int32   nbr[8]           the neighbours' view indices in the caller's order; an index outside
+ *                                                          0..n-1 or equal to i is skipped (so a corrupt table reads nothing out of range)
+ *                 words 10..21    float32 bc[12]           B (3x3 row-major) | c (3) of view i itself, as sfm_mvs_consistency's bc_host
+ *                 words 22..117   float32 ab[8][12]        A (3x3 row-major) | b (3) per neighbour slot, as sfm_mvs_consistency's ab_host
+ *                 words 118..127  unused (padding; not read)
+ *   1 <= n <= 4096, 1 <= w, h <= 32767, tau finite and >= 0, cos_min not NaN (-inf and +inf are accepted)
+ *   Per pixel (x, y) of view i, with d = depth[i][y][x], n = normal[i][y][x] (three words) and the record R_i:
+ *     projection  for slot s = 0 .. min(nnbr, 8)-1 with v = nbr[s] (not skipped) and a = ab[s]:
+ *                 p_k = d*((a_k0*x + a_k1*y) + a_k2) + b_k as sfm_mvs_consistency; the slot is consistent iff d > 0, p_2 > 0,
+ *                 (u, t) = (floor(p_0/p_2 + 0.5), floor(p_1/p_2 + 0.5)) lies in the frame (0 <= u <= w-1, 0 <= t <= h-1),
+ *                 dv = depth[v][t][u] > 0, |p_2 - dv| <= tau*dv, and, when normal_dev is given, with m = normal[v][t][u]:
+ *                 (n_0*m_0 + n_1*m_1) + n_2*m_2 >= cos_min (false for a NaN; cos_min = -inf passes every non-NaN product)
+ *     counting    count = the consistent slots (a view listed twice counts twice); lower = one of them has v < i
+ *     keep        d > 0 && count >= min_consistent && !(unique && lower): sfm_mvs_consistency's rule; k = 1 + count
+ *     position    X_k = d*((B_k0*x + B_k1*y) + B_k2) + c_k from R_i.bc (sfm_mvs_consistency's xyz word); then, for every consistent
+ *                 slot in order, X_k = X_k + (dv*((B'_k0*u + B'_k1*t) + B'_k2) + c'_k) with B' | c' = R_v.bc (the neighbour's own sample
+ *                 at its own pixel); xyz_k = X_k / (float)k
+ *     normal      N = n; N_k = N_k + m_k for every consistent slot in order; len = sqrtf((N_0*N_0 + N_1*N_1) + N_2*N_2);
+ *                 normal_out_k = len > 0 ? N_k / len : n_k  (a zero or NaN length gives the pixel's own normal back)
+ *     colour      per channel S = the byte of the pixel + the bytes of the consistent slots' pixels (u, t) (integers);
+ *                 bgr_out = (2*S + k) / (2*k) in integer division: the mean rounded half up, exact and order-free
+ *   mask_dev        [n][h][w] uint8 1 = kept, else 0
+ *   xyz_dev         [n][h][w][3] float32
+ *   normal_out_dev  [n][h][w][3] float32, written iff normal_dev is given
+ *   bgr_out_dev     [n][h][w][3] uint8, written iff bgr_dev is given
+ *   support_dev     [n][h][w] uint8 k
+ *   Every output is 0 where the mask is 0.  Whether an optional input is present changes no other output (normal_dev = NULL
+ *   gives the mask and positions of cos_min = -inf, unless a NaN normal fails the product).  Two identities: with normal_dev = NULL (or
+ *   cos_min = -inf and no NaN normal) the mask of view i is sfm_mvs_consistency's for its neighbour list; where support is 1, xyz
+ *   is sfm_mvs_consistency's xyz word for word (one term, and x / 1.0f = x).
+ * No workspace beyond the table, no atomics, no host wait; a second run gives the same bits.
+ * ---------------------------------------------------------------------- */
+int sfm_mvs_fuse(const float* depth_dev, const float* normal_dev, const uint8_t* bgr_dev, const void* table_dev, int n, int64_t w,
+                 int64_t h, float tau, float cos_min, int unique, uint8_t* mask_dev, float* xyz_dev, float* normal_out_dev,
+                 uint8_t* bgr_out_dev, uint8_t* support_dev, void* stream);
+
+/* ------------------------------------------------------------------------
  * MESH a surface from the MVS depth maps     after sfm.py:298 (`densify`)
  *
  * Volumetric fusion of depth maps into a truncated signed distance field (TSDF) and its zero set by marching tetrahedra

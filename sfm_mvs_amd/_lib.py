@@ -96,6 +96,7 @@ SIGNATURES = {
     "sfm_mvs_cost_depth": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "sfm_mvs_patchmatch": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _int, _int, _f32, _f32, _vp, _int, _int, _f32, _f32, _c.c_uint32,
                                   _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_mvs_fuse": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _f32, _f32, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sfm_tsdf_integrate": (_int, [_vp, _vp, _vp, _vp, _int, _i64, _i64, _vp, _f32, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "sfm_mesh_count_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sfm_mesh_count": (_int, [_vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _sz, _vp]),

@@ -1,8 +1,8 @@
 """Plane-sweep multi-view stereo: the dense half of sfm-mvs (sfm.py:298 `densify = False`; the dense.ply branch of to_ply,
 sfm.py:194-201, that the reference never feeds).
 
-Thin, validating wrappers over `sfm_mvs_plane_sweep` and `sfm_mvs_consistency` (include/sfm_hip.h): device tensors in, device
-tensors out, stream ordered, no CPU path.  The host part is the geometry of a handful of 3x3 matrices per view (float64, cast
+Thin, validating wrappers over `sfm_mvs_plane_sweep` and `sfm_mvs_consistency` (include/sfm_hip.h) and the opt-in steps between and
+after them (aggregation, PatchMatch refinement, merging fusion): device tensors in, device tensors out, stream ordered, no CPU path.  The host part is the geometry of a handful of 3x3 matrices per view (float64, cast
 once to float32) and the choice of the depth range from the sparse cloud.  docs/mvs.md describes the algorithm and its numbers.
 """
 import ctypes
@@ -335,6 +335,118 @@ def patchmatch_refine(ref, srcs, mv, qmin, qmax, depth_init=None, K=None, P_ref=
     return depth, cost, nrm, state
 
 
+# Default of the opt-in merging fusion (run_mvs(fuse=True)): the smallest angle of the grid of scripts/calibrate_mvs_fuse.py that keeps
+# >= 95 % of the unbounded point count on both scenes under refine=True on every seed (tests/golden/mvs_fuse_calibration.json;
+# docs/mvs.md §10)
+FUSE_MAX_ANGLE = 45.0   # degrees between the normals of a pixel and of a consistent neighbour's pixel
+
+# One view's record of sfm_mvs_fuse's table (include/sfm_hip.h, "MVS-FUSE"): 512 bytes, view indices only
+FUSE_RECORD = np.dtype([("nnbr", np.int32), ("min_consistent", np.int32), ("nbr", np.int32, (MAX_VIEWS,)), ("bc", np.float32, (12,)),
+                        ("ab", np.float32, (MAX_VIEWS, 12)), ("pad", np.int32, (10,))])
+assert FUSE_RECORD.itemsize == 512
+FUSE_MAX_N = 4096
+
+
+def fuse_table(K, Ps, nbrs, min_consistent=2):
+    """The host table of sfm_mvs_fuse: a FUSE_RECORD per view with its neighbours' indices in the caller's order, its own `bc` and one
+    `ab` per neighbour (consistency_matrices, unchanged) and min(min_consistent, len(nbrs[i])), as run_mvs caps it per view.
+    K 3x3, Ps [n, 3, 4], nbrs per view a list of at most MAX_VIEWS view indices (none the view itself)."""
+    Ps = np.asarray(Ps, np.float64).reshape(-1, 3, 4)
+    nbrs = _checked_neighbours(nbrs, len(Ps))
+    mc = int(min_consistent)
+    if mc < 0:
+        raise SfmHipError(f"fuse_table: min_consistent {mc} is negative")
+    # consistency_matrices' words with every camera decomposed once (the table is made before the first launch, while the device idles):
+    # the same float64 expressions in the same order as _relative and consistency_matrices, cast once
+    K = np.asarray(K, np.float64)
+    Kinv = np.linalg.inv(K)
+    rts = [_rt(K, P) for P in Ps]
+    table = np.zeros(len(Ps), FUSE_RECORD)
+    for i, row in enumerate(nbrs):
+        Rr, tr = rts[i]
+        ab = np.empty((len(row), 12), np.float64)
+        for s, v in enumerate(row):
+            Ro, to = rts[v]
+            Rrel = Ro @ Rr.T
+            ab[s, :9], ab[s, 9:] = (K @ Rrel @ Kinv).ravel(), K @ (to - Rrel @ tr)
+        table[i]["nnbr"], table[i]["min_consistent"] = len(row), min(mc, len(row))
+        table[i]["nbr"][:len(row)] = row
+        table[i]["bc"] = np.concatenate([(Rr.T @ Kinv).ravel(), -Rr.T @ tr]).astype(np.float32)
+        table[i]["ab"][:len(row)] = ab.astype(np.float32)
+    return table
+
+
+def _cos_min(max_angle):
+    """cos_min of sfm_mvs_fuse for a bound in degrees (None: -inf, the test is off): the cosine in float64, cast once."""
+    if max_angle is None:
+        return float("-inf")
+    a = float(max_angle)
+    if not 0.0 <= a <= 180.0:
+        raise SfmHipError(f"fuse: max_angle must be None or an angle of 0..180 degrees (got {max_angle!r})")
+    return float(np.float32(np.cos(np.deg2rad(np.float64(a)))))
+
+
+def fuse(depths, table, normals=None, frames=None, tau=0.01, max_angle=None, unique=True):
+    """Merging fusion of the stacked depth maps of all views in one launch (sfm_mvs_fuse; docs/mvs.md §10).
+    depths [n, H, W] float32, normals [n, H, W, 3] float32 or None, frames [n, H, W, 3] uint8 or None: contiguous device tensors;
+    table: fuse_table's array (uploaded pinned and stream-ordered) or a uint8 [n, 512] device tensor already uploaded;
+    max_angle: degrees (None: normals are averaged but not tested).
+    Returns dict(mask [n, H, W] uint8, xyz [n, H, W, 3] float32, normals [n, H, W, 3] float32 or None, colors [n, H, W, 3] uint8 or
+    None, support [n, H, W] uint8: the samples merged, 1 + the consistent neighbours).  No host wait."""
+    if not torch.is_tensor(depths) or depths.dtype != torch.float32 or depths.dim() != 3:
+        raise SfmHipError("fuse: depths must be an [n, H, W] float32 device tensor")
+    require_cuda(depths, normals, frames)
+    n, h, w = depths.shape
+    dev = depths.device
+    if not 1 <= n <= FUSE_MAX_N or not (1 <= w <= 32767 and 1 <= h <= 32767):
+        raise SfmHipError(f"fuse: {n} views of {w} x {h}: needs 1..{FUSE_MAX_N} views and sides of 1..32767")
+    for t, dt, what in ((depths, torch.float32, "depths"), (normals, torch.float32, "normals"), (frames, torch.uint8, "frames")):
+        if t is None:
+            continue
+        want = (n, h, w) if what == "depths" else (n, h, w, 3)
+        if tuple(t.shape) != want or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise SfmHipError(f"fuse: {what} must be a contiguous {want} {dt} tensor on the depths' device")
+    tau = float(tau)
+    if not (0.0 <= tau < np.inf):
+        raise SfmHipError("fuse: tau must be finite and >= 0")
+    cos_min = _cos_min(max_angle)
+    if torch.is_tensor(table):
+        require_cuda(table)
+        if table.dtype != torch.uint8 or tuple(table.shape) != (n, FUSE_RECORD.itemsize) or table.device != dev or not table.is_contiguous():
+            raise SfmHipError(f"fuse: a device table must be a contiguous uint8 [{n}, {FUSE_RECORD.itemsize}] tensor on the depths' device")
+        table_dev = table
+    else:
+        table = np.asarray(table)
+        if table.dtype != FUSE_RECORD or table.shape != (n,):
+            raise SfmHipError(f"fuse: the table must hold one FUSE_RECORD per view ({n}); fuse_table makes it")
+        table_dev = _upload(table.view(np.uint8).reshape(n, FUSE_RECORD.itemsize), dev)
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    support = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    nout = None if normals is None else torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+    cout = None if frames is None else torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    with on_device(dev):
+        check(_lib.lib().sfm_mvs_fuse(ptr(depths), ptr(normals), ptr(frames), ptr(table_dev), n, w, h, tau, cos_min, 1 if unique else 0,
+                                      ptr(mask), ptr(xyz), ptr(nout), ptr(cout), ptr(support), stream_ptr()), "sfm_mvs_fuse")
+    return dict(mask=mask, xyz=xyz, normals=nout, colors=cout, support=support)
+
+
+_FUSE_KEYS = ("max_angle", "colours")
+
+
+def _checked_fuse(fuse_opt):
+    """run_mvs's `fuse` keyword as dict(max_angle, colours) (None: the filter), or an SfmHipError."""
+    if fuse_opt is None or fuse_opt is False:
+        return None
+    if fuse_opt is True:
+        fuse_opt = {}
+    if not isinstance(fuse_opt, dict) or any(k not in _FUSE_KEYS for k in fuse_opt):
+        raise SfmHipError(f"run_mvs: fuse must be None, True or a dict with keys among {_FUSE_KEYS}")
+    opts = dict(max_angle=fuse_opt.get("max_angle", FUSE_MAX_ANGLE), colours=bool(fuse_opt.get("colours", True)))
+    _cos_min(opts["max_angle"])
+    return opts
+
+
 _REFINE_KEYS = ("iters", "far", "depth_step", "slope_step", "seed")
 
 
@@ -382,7 +494,7 @@ def _checked_ranges(ranges, n, ndepth):
 
 
 def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_min=VAR_MIN, cost_max=COST_MAX, tau=0.01,
-            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8, neighbours=None, ranges=None, refine=None):
+            min_consistent=2, unique=True, aggregate=False, shift=None, p1=P1, p2=P2, ndir=8, neighbours=None, ranges=None, refine=None, fuse=None):
     """Dense reconstruction of a registered sequence: a plane-sweep depth map per view, geometric-consistency filtering, and one
     coloured cloud.
 
@@ -406,6 +518,13 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
              winner-take-all one, or the aggregated one) is refined over slanted planes before the consistency pass, with the view's
              own sources and plane range (docs/mvs.md §9).  The result gains "normal_maps" (per view (H, W, 3) float32 device tensor:
              unit world normals facing the camera, 0 where there is no depth) and "normals" (m, 3) float64, the points' normals.
+    fuse:    None, True or a dict of max_angle (degrees, default FUSE_MAX_ANGLE; None: no bound) and colours (default True): the
+             per-view consistency filter is replaced by one launch of the merging fusion (`fuse`, sfm_mvs_fuse; docs/mvs.md §10).  A
+             kept pixel is emitted as the mean of its own sample and its consistent neighbours' samples: `points` the averaged
+             positions, `colors` the averaged colours (colours=False: the pixel's own), with refine `normals` the normalised sum of
+             the normals, and a neighbour whose normal is more than max_angle away from the pixel's is not consistent.  Without
+             refine there are no normals: positions and colours only.  The result gains "support" (m,) uint8, the samples merged
+             per point; `depths` / `normal_maps` are then views of one [n, H, W] / [n, H, W, 3] stack.
     Returns dict(depths [per view (H, W) float32 device tensor], points (m, 3) float64, colors (m, 3) float64 B G R): shaped as
     Xtot / colorstot, so that pipeline.to_ply(path, points, colors, densify=True) writes Point_Cloud/dense.ply.
     One host wait per call: the fused point count (then one download of the points and colours); every upload is stream-ordered
@@ -424,6 +543,7 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     nbrs = [_sequence_neighbours(i, n, nsrc) for i in range(n)] if neighbours is None else _checked_neighbours(neighbours, n)
     planes = None if ranges is None else _checked_ranges(ranges, n, ndepth)
     refine = _checked_refine(refine)
+    fuse_opt = _checked_fuse(fuse)
     dev = torch.device("cuda", torch.cuda.current_device())
     if all(torch.is_tensor(im) and im.is_cuda for im in images):
         frames = [im.to(dev).contiguous() for im in images]
@@ -440,6 +560,10 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     if planes is None:
         planes = np.stack([_inverse_depths_host(*depth_range(Xtot, Ps[i], P_all=Ps), ndepth) for i in range(n)])
     invd = _upload(planes, dev)
+    if fuse_opt is not None:                                    # the table too goes up before the first launch; the maps are stacked
+        table_dev = _upload(fuse_table(K, Ps, nbrs, min_consistent).view(np.uint8).reshape(n, FUSE_RECORD.itemsize), dev)
+        dstack = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+        nstack = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if refine is not None else None
     depths, normal_maps = [], []
     if aggregate:
         vol = torch.empty((int(ndepth), h, w), dtype=torch.float32, device=dev)
@@ -447,9 +571,9 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
         sbuf = torch.empty((int(ndepth), h, w), dtype=torch.uint16, device=dev)
     for i in range(n):
         if not nbrs[i]:                                         # no source: no sweep, an all-zero map
-            depths.append(torch.zeros((h, w), dtype=torch.float32, device=dev))
+            depths.append(torch.zeros((h, w), dtype=torch.float32, device=dev) if fuse_opt is None else dstack[i].zero_())
             if refine is not None:
-                normal_maps.append(torch.zeros((h, w, 3), dtype=torch.float32, device=dev))
+                normal_maps.append(torch.zeros((h, w, 3), dtype=torch.float32, device=dev) if fuse_opt is None else nstack[i].zero_())
             continue
         mv = sweep_matrices(K, Ps[i], Ps[nbrs[i]])
         if aggregate:
@@ -460,8 +584,10 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
         if refine is not None:
             d, _, nm, _ = patchmatch_refine(grays[i], [grays[v] for v in nbrs[i]], mv, planes[i, 0], planes[i, -1], d, K, Ps[i], radius,
                                             min(topk, len(nbrs[i])), var_min, cost_max, **refine)
-            normal_maps.append(nm)
-        depths.append(d)
+            normal_maps.append(nm if fuse_opt is None else nstack[i].copy_(nm))
+        depths.append(d if fuse_opt is None else dstack[i].copy_(d))
+    if fuse_opt is not None:
+        return _fused_result(depths, normal_maps, dstack, nstack, torch.stack(frames), table_dev, tau, unique, fuse_opt)
     masks = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
     xyz = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
     for i in range(n):
@@ -479,4 +605,21 @@ def run_mvs(images, K, posearr, Xtot, ndepth=128, radius=3, nsrc=4, topk=2, var_
     out = dict(depths=depths, points=np.ascontiguousarray(both[:, :3]), colors=np.ascontiguousarray(both[:, 3:6]))
     if refine is not None:
         out.update(normal_maps=normal_maps, normals=np.ascontiguousarray(both[:, 6:]))
+    return out
+
+
+def _fused_result(depths, normal_maps, dstack, nstack, fstack, table_dev, tau, unique, fuse_opt):
+    """run_mvs's result with fuse: the one launch over the stacked maps, the one host wait (the point count), one download."""
+    from . import ops
+    res = fuse(dstack, table_dev, nstack, fstack if fuse_opt["colours"] else None, tau, fuse_opt["max_angle"], unique)
+    idx = ops.mask_indices(res["mask"]).long()                  # the one host wait: the count sizes the result
+    cols = [res["xyz"].reshape(-1, 3)[idx].double(), (fstack if res["colors"] is None else res["colors"]).reshape(-1, 3)[idx].double(),
+            res["support"].reshape(-1, 1)[idx].double()]
+    if nstack is not None:
+        cols.append(res["normals"].reshape(-1, 3)[idx].double())
+    both = torch.cat(cols, 1).cpu().numpy()
+    out = dict(depths=depths, points=np.ascontiguousarray(both[:, :3]), colors=np.ascontiguousarray(both[:, 3:6]),
+               support=both[:, 6].astype(np.uint8))
+    if nstack is not None:
+        out.update(normal_maps=normal_maps, normals=np.ascontiguousarray(both[:, 7:]))
     return out

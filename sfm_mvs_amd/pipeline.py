@@ -313,7 +313,7 @@ def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=
     profile: a DriverProfile — the run is then a PROFILED one (the device is drained at every stage boundary).
     densify: sfm.py:298's global — True runs the plane-sweep MVS (mvs.run_mvs, keyword arguments `mvs_options`) on the halved
     frames already in HBM after the chain and sets out["dense"] (points / colors for to_ply(..., densify=True)); False changes
-    nothing.
+    nothing.  A dict is True with its entries as further run_mvs keywords (over `mvs_options`), e.g. densify=dict(fuse=True).
     aggregate: with densify, True / False sets run_mvs's `aggregate` (shiftable windows + semi-global aggregation of every view's
     cost volume, docs/mvs.md §7); None leaves it to `mvs_options`.
     mesh: True (needs densify) also fuses the depth maps into a surface (mesh.run_mesh on the same halved frames, keyword
@@ -325,6 +325,8 @@ def run_sfm_images(images, K, downscale=2, log=None, be=None, bundle_adjustment=
         from . import mvs
         small = out.pop("_small")
         opts = dict(mvs_options or {})
+        if isinstance(densify, dict):
+            opts.update(densify)
         if aggregate is not None:
             opts["aggregate"] = bool(aggregate)
         out["dense"] = mvs.run_mvs(small, K, out["posearr"], out["Xtot"], **opts)
@@ -622,20 +624,29 @@ def common_points(pts1, pts2, pts3):
     return indx1, indx2, pts2[keep].reshape(-1, 2), pts3[keep].reshape(-1, 2)
 
 
-def to_ply(path, point_cloud, colors, densify=False):
+def to_ply(path, point_cloud, colors, densify=False, normals=None):
     """sfm.py:169-201 byte-for-byte: x200, keep dist < mean(dist)+300 about the centroid, tab-indented header
-    whose last line also indents the first vertex (quirk 9), colour columns written as B G R."""
+    whose last line also indents the first vertex (quirk 9), colour columns written as B G R.
+    normals ((m, 3), e.g. mvs.run_mvs(refine=True, fuse=True)["normals"]): written unscaled as `property float nx`, `ny`, `nz` after
+    `z`, the centroid cut applied to their rows too; without them the file is byte for byte what it always was."""
     pts = point_cloud.reshape(-1, 3) * 200
-    verts = np.hstack([pts, colors.reshape(-1, 3)])
+    extra = []
+    if normals is not None:
+        extra = [np.asarray(normals, np.float64).reshape(-1, 3)]
+        if len(extra[0]) != len(pts):
+            raise ValueError(f"to_ply: {len(pts)} points but {len(extra[0])} normals")
+    verts = np.hstack([pts] + extra + [colors.reshape(-1, 3)])
     centred = verts[:, :3] - np.mean(verts[:, :3], axis=0)
     dist = np.sqrt(centred[:, 0] ** 2 + centred[:, 1] ** 2 + centred[:, 2] ** 2)
     verts = verts[np.where(dist < np.mean(dist) + 300)]
-    lines = ["format ascii 1.0", "element vertex %d" % len(verts), "property float x", "property float y",
-             "property float z", "property uchar blue", "property uchar green", "property uchar red", "end_header"]
+    lines = ["format ascii 1.0", "element vertex %d" % len(verts), "property float x", "property float y", "property float z"]
+    if normals is not None:
+        lines += ["property float nx", "property float ny", "property float nz"]
+    lines += ["property uchar blue", "property uchar green", "property uchar red", "end_header"]
     name = "dense.ply" if densify else "sparse.ply"
     with open(path + "/Point_Cloud/" + name, "w") as f:
         f.write("ply\n" + "".join("\t\t" + ln + "\n" for ln in lines) + "\t\t")
-        np.savetxt(f, verts, "%f %f %f %d %d %d")
+        np.savetxt(f, verts, "%f %f %f %d %d %d" if normals is None else "%f %f %f %f %f %f %d %d %d")
     return len(verts)
 
 
