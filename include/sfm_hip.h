@@ -1282,6 +1282,102 @@ int sfm_track_ba_step(int64_t ncam, int64_t npt, const int32_t* track_off_dev, c
                       double* dc_dev, double* dp_dev, int32_t* iters_host, int32_t* status_host, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * TRACKS-CAL (no reference counterpart; csrc/tracks_cal.hip, docs/tracks.md §15): TRACKS-BA with one set of intrinsics shared by all
+ * images among the unknowns, and the undistortion that goes with the model.  Opt-in: nothing of TRACKS-BA changes.
+ *
+ * Camera model.  theta = (f, cx, cy, k1, k2), float64, shared by all images; a fixed aspect a = K[1][1] / K[0][0] from the caller's K,
+ *   no skew.  With X' = R(rvec) X + t, x = X'/Z', y = Y'/Z', r2 = x*x + y*y, d = 1 + k1*r2 + k2*r2*r2:
+ *       u = f*d*x + cx        v = a*f*d*y + cy
+ *   (products from the left: (f*d)*x, ((a*f)*d)*y; d = (1 + k1*r2) + (k2*r2)*r2).  With k1 = k2 = 0 this is the projection of
+ *   sfm_track_ba_sweep term for term (fy = a*f).  A bit mask `free` (bit i frees theta[i]: 1 f, 2 cx, 4 cy, 8 k1, 16 k2) chooses
+ *   what moves; it acts in sfm_track_cal_step only.
+ *
+ * The problem layout, the CSRs, the "no index is trusted" rules, the chunks, the active-set rules (mode 0 writes active_dev, mode 1
+ *   reads it and counts `crossed`), the Huber weight and cost, stat_dev and count_dev are those of TRACKS-BA.  The workspace again
+ *   belongs to ONE linearisation; the rows start at its first 256-byte aligned address: float64 [nobs][30], 240 bytes each.
+ *
+ * sfm_track_cal_sweep — linearisation at (cams, theta_host - dtheta_dev, X).  theta_host float64 [5] is checked on the host;
+ *   dtheta_dev float64 [5] (may be NULL: zero) is a step that is still on the device, subtracted by every lane, so that a trial
+ *   sweep needs no host wait for the step of theta.  Where the difference has f <= 0 or a non-finite entry no observation passes
+ *   the active test (mode 0: none is active; mode 1: every active one counts in `crossed`).
+ *   rows     per observation 30 doubles, each times sqrt(w): Jc (d(u,v)/d(rvec,tvec), 2 x 6: the u row, then the v row), Ji
+ *            (d(u,v)/d theta, 2 x 5: u row (d*x, 1, 0, f*x*r2, f*x*r2*r2), v row (a*d*y, 0, 1, a*f*y*r2, a*f*y*r2*r2)), Jp (d(u,v)/dX,
+ *            2 x 3), r (2).  Rows of observations that do not contribute are all zero.
+ *   blocks   JtJ_cam_dev [ncam][36], Jtr_cam_dev [ncam][6], JtJ_pt_dev [npt][9], Jtr_pt_dev [npt][3] as TRACKS-BA.
+ *   border   E_dev [ncam][30] = E_i = sum Jc^T Ji (6 x 5, row-major);  G_dev [25] = sum Ji^T Ji, written in full;  Jtr_theta_dev [5]
+ *            = g_i = sum Ji^T r;  F_dev [npt][15] = F_j = sum Jp^T Ji (3 x 5, row-major).  The columns of parameters that are not
+ *            free are computed all the same.
+ *
+ * Summation order — the contract.  THERE ARE NO FLOATING-POINT ATOMICS in csrc/tracks_cal.hip.
+ *   point side (C_j, g_p, F_j, out of product mode 0) and camera side (B_i, g_c, E_i, out of product mode 1): as TRACKS-BA; a chunk's
+ *                27 values grow by the 30 of E_i.
+ *   G, g_i, out_theta and the cost: a workgroup tree over 256 consecutive observations, then one workgroup of 1024 lanes folding the
+ *                block sums (lane l the blocks l, l + 1024, ... ascending, then a tree).
+ *   A second run gives the same bits.  Appending cameras and tracks that do not observe a problem's points leaves the problem's
+ *   per-camera and per-point blocks (B_i, g_c, E_i, C_j, g_p, F_j) and its rows bit for bit.  The values are held to 1e-10 of the
+ *   largest entry against tests/np_track_cal.py.
+ *
+ * sfm_track_cal_product — over the rows a sweep left in ws_dev:
+ *   mode 0: (in [ncam][6], in_theta [5]) -> out [npt][3] = sum_o Jp^T (Jc in[cam_idx[o]] + Ji in_theta)   (out_theta unused)
+ *   mode 1: in [npt][3] -> out [ncam][6] = sum_o Jc^T (Jp in[pt_idx[o]]) and out_theta [5] = sum_o Ji^T (Jp in[pt_idx[o]])
+ *   (in_theta unused; out_theta sums the observations whose two indices are in range).
+ *
+ * sfm_track_cal_step — one damped step on the bordered system.  Unknowns y = (dc, di), 6 ncam + 5 entries;
+ *   S = [Bd E; E^T Gd] - [W; F^T] Cd^-1 [W^T F], the diagonals of B, G and C times (1 + lam) (Marquardt: the step does not depend on
+ *   the very different scales of f and k1);  S y = (g_c, g_i) - [W; F^T] Cd^-1 g_p by conjugate gradients preconditioned with
+ *   blockdiag(Bd^-1, Gd^-1), the recurrence and the single-workgroup vector kernels of sfm_track_ba_step, with two guards: alpha = 0
+ *   unless p.Sp > 0 and beta = 0 unless r.z > 0 (with a handful of unknowns, one free parameter and a fixed camera say, the residual
+ *   reaches exactly 0 between two looks of the host; the iterations that remain are then no-ops instead of 0 / 0);
+ *   dp = Cd^-1 (g_p - W^T dc - F di).  The update is parameters - step.
+ *   free         a parameter that is not free has its row and column of the system replaced by the identity and a zero right-hand
+ *                side: its entry of dtheta_dev is exactly 0.  Gd^-1 is the inverse of Gd so restricted.
+ *   fix_first_camera, iters_host, the host waits (one per look at r.r before iterations 0, 5, 10, ...) as sfm_track_ba_step.
+ *   status_host  bits 0 and 1 as sfm_track_ba_step; bit 2: Gd restricted to the free set is singular (a zero or non-finite pivot;
+ *                its preconditioner block is the identity).
+ *
+ * sfm_undistort_points — px_dev float32 [n][2] pixels of the distorted image -> out_dev float32 [n][2] pixels of the ideal pinhole
+ *   image with K_out_host (float64 [9]; fx', fy', cx', cy' are read).  In float64, without contraction, in this order:
+ *   xd = (u - cx) / f, yd = (v - cy) / (a*f), rd = sqrt(xd*xd + yd*yd); r = rd, then TEN times, without a data-dependent exit,
+ *   r2 = r*r, g = r*(1 + r2*(k1 + k2*r2)) - rd, h = 1 + r2*(3*k1 + 5*k2*r2), r = r - g/h;  s = r/rd (1 when rd = 0);
+ *   out = float32(fx'*(xd*s) + cx', fy'*(yd*s) + cy').  A non-finite input or result gives NaN in both coordinates.  0 <= n <= 2^31-1.
+ *
+ * sfm_undistort_image — src_dev uint8 [nimg][H][W][C], C in {1, 3} -> dst_dev of the same shape (another buffer) and, when
+ *   mask_dev is not NULL, uint8 [nimg][H][W] of 0 / 1: one BATCHED call, no host wait.  Every output pixel (xo, yo) is mapped forward
+ *   in float64: x = (xo - cx')/fx', y = (yo - cy')/fy', r2, d as above, su = float32(f*d*x + cx), sv = float32(a*f*d*y + cy).
+ *   It is valid iff 0 <= su <= W-1 and 0 <= sv <= H-1, i.e. iff none of the four taps x0 = floor(su), x0 + 1, y0 = floor(sv), y0 + 1
+ *   that carry weight is outside (a tap past the last column or row has weight exactly 0 and is read at W-1, H-1).  In float32,
+ *   without contraction, ax = su - x0, ay = sv - y0, top = p00 + ax*(p10 - p00), bot = p01 + ax*(p11 - p01),
+ *   val = top + ay*(bot - top), out = floor(val + 0.5) (round half up) clamped to 0..255.  An invalid pixel is 0 in every channel and
+ *   0 in the mask.  With k1 = k2 = 0 and K_out = K the image comes back byte for byte.  0 <= nimg <= 65535, 1 <= H, W <= 65536.
+ *   Both undistortions match tests/np_track_cal.py to the bit.
+ *
+ * Errors (SFM_ERR_ARG / SFM_ERR_WORKSPACE, before any device call): those of TRACKS-BA (the border arrays, dtheta_dev of the step and
+ *   the theta vectors of the product among the pointers that must not be NULL), and: an entry of theta_host not finite, f <= 0,
+ *   a <= 0 or not finite, free outside 0..31, channels outside {1, 3}, K_out not finite or without positive focal lengths, sizes of
+ *   the undistortions outside their limits, src_dev == dst_dev.  sfm_track_cal_ws_bytes is 0 for invalid sizes (240 bytes per
+ *   observation for the rows, 456 per chunk, 240 per 256 observations, the step's vectors).
+ * ---------------------------------------------------------------------- */
+size_t sfm_track_cal_ws_bytes(int64_t ncam, int64_t npt, int64_t nobs);
+int sfm_track_cal_sweep(const double* cams_dev, int64_t ncam, const double* theta_host, double aspect, const double* dtheta_dev,
+                        const double* X_dev, int64_t npt, const float* obs_dev, const int32_t* track_off_dev, const int32_t* cam_idx_dev,
+                        const int32_t* pt_idx_dev, const int32_t* cam_off_dev, const int32_t* cam_obs_dev, int64_t nobs, double huber, int mode,
+                        uint8_t* active_dev, double* JtJ_cam_dev, double* Jtr_cam_dev, double* JtJ_pt_dev, double* Jtr_pt_dev, double* E_dev,
+                        double* G_dev, double* Jtr_theta_dev, double* F_dev, double* stat_dev, int32_t* count_dev, void* ws_dev, size_t ws_bytes,
+                        void* stream);
+int sfm_track_cal_product(int64_t ncam, int64_t npt, const int32_t* track_off_dev, const int32_t* cam_idx_dev, const int32_t* pt_idx_dev,
+                          const int32_t* cam_off_dev, const int32_t* cam_obs_dev, int64_t nobs, int mode, const double* in_dev,
+                          const double* in_theta_dev, double* out_dev, double* out_theta_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int sfm_track_cal_step(int64_t ncam, int64_t npt, const int32_t* track_off_dev, const int32_t* cam_idx_dev, const int32_t* pt_idx_dev,
+                       const int32_t* cam_off_dev, const int32_t* cam_obs_dev, int64_t nobs, const double* JtJ_cam_dev, const double* Jtr_cam_dev,
+                       const double* JtJ_pt_dev, const double* Jtr_pt_dev, const double* E_dev, const double* G_dev, const double* Jtr_theta_dev,
+                       double lam, int free_mask, int fix_first_camera, double cg_tol, int cg_iters, double* dc_dev, double* dtheta_dev,
+                       double* dp_dev, int32_t* iters_host, int32_t* status_host, void* ws_dev, size_t ws_bytes, void* stream);
+int sfm_undistort_points(const float* px_dev, int64_t n, const double* theta_host, double aspect, const double* K_out_host, float* out_dev,
+                         void* stream);
+int sfm_undistort_image(const uint8_t* src_dev, int64_t nimg, int64_t H, int64_t W, int channels, const double* theta_host, double aspect,
+                        const double* K_out_host, uint8_t* dst_dev, uint8_t* mask_dev, void* stream);
+
+/* ------------------------------------------------------------------------
  * MVS-PLAN (no reference counterpart; csrc/mvs_plan.hip, docs/mvs.md §8): the sources and the depth range of every view of the plane
  * sweep from the sparse model, i.e. from the point-major observations of TRACKS-BA's problem layout (track_off_dev [npt + 1], cam_idx_dev,
  * pt_idx_dev [nobs], cam_off_dev [ncam + 1], cam_obs_dev [nobs]), X_dev FLOAT64 [npt][3] and P_dev float64 [ncam][12].

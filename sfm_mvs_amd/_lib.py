@@ -132,6 +132,14 @@ SIGNATURES = {
     "sfm_track_ba_product": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _sz, _vp]),
     "sfm_track_ba_step": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _int, _f64, _int, _vp, _vp,
                                  _c.POINTER(_i32), _c.POINTER(_i32), _vp, _sz, _vp]),
+    "sfm_track_cal_ws_bytes": (_sz, [_i64, _i64, _i64]),
+    "sfm_track_cal_sweep": (_int, [_vp, _i64, _vp, _f64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _int, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_cal_product": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sfm_track_cal_step": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _int, _int, _f64, _int,
+                                  _vp, _vp, _vp, _c.POINTER(_i32), _c.POINTER(_i32), _vp, _sz, _vp]),
+    "sfm_undistort_points": (_int, [_vp, _i64, _vp, _f64, _vp, _vp, _vp]),
+    "sfm_undistort_image": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _f64, _vp, _vp, _vp, _vp]),
     "sfm_view_pair_counts": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "sfm_view_depth_ranges": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "sfm_view_select": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),

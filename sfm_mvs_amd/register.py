@@ -290,6 +290,18 @@ class _HipEngine:
         cams, _, hist, info = track_ba.bundle_adjust_tracks(_upload(cams0, self.dev), self.K, X.to(torch.float64), obs, cam_ba, pt.contiguous(), **kw)
         return track_ba.P_from_cams(cams.cpu().numpy(), self.K), hist, info
 
+    def bundle_calibrated(self, order, P, model, calibrate, **kw):
+        """`bundle` with track_cal.bundle_adjust_calibrated (docs/tracks.md §15): the rows of P are built with K'; info gains K, dist."""
+        from . import track_ba, track_cal
+        X, obs, cam, pt, _ = self._model(model)
+        rank = np.full(self.n_img, -1, np.int32)
+        rank[np.asarray(order)] = np.arange(len(order), dtype=np.int32)
+        cam_ba = _upload(rank, self.dev).index_select(0, cam.long()).contiguous()
+        cams0 = track_ba.cams_from_P(np.asarray(P, np.float64)[np.asarray(order)], self.K)
+        cams, _, K_new, dist, hist, info = track_cal.bundle_adjust_calibrated(_upload(cams0, self.dev), self.K, calibrate.get("dist"), X.to(torch.float64), obs,
+                                                                              cam_ba, pt.contiguous(), free=calibrate.get("free", ("f", "k1")), **kw)
+        return track_ba.P_from_cams(cams.cpu().numpy(), K_new), hist, dict(info, K=K_new, dist=dist)
+
     def result(self, model):
         """The ONE download at the end: the keys of run_tracks(robust=True) for the final model."""
         X, obs, cam, pt, off = self._model(model)
@@ -332,7 +344,7 @@ def _pair_config(pair_config, n_pairs):
 
 
 def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_seed=MIN_SEED, seed_tries=5, max_tries=2, pnp=None,
-                  ba_every=BA_EVERY, ba=None, log=None, pair_config=None):
+                  ba_every=BA_EVERY, ba=None, log=None, pair_config=None, calibrate=None):
     """The loop of `register_tracks` on an engine (see `_HipEngine` for what one provides).  Argument errors are raised before the engine
     does any work."""
     n_img = int(n_img)
@@ -428,12 +440,20 @@ def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_s
             since_ba = 0
         model = eng.round(registered, P)
         rounds += 1
-    if (since_ba or not histories) and model["points"]:
+    calibrated = None
+    if calibrate is not None and model["points"]:                      # the FINAL adjustment is the calibrated one; the rounds before it are untouched
+        P[order], hist, calibrated = eng.bundle_calibrated(order, P, model, calibrate, **ba)
+        histories.append(hist)
+        model = eng.round(registered, P)
+        rounds += 1
+    elif (since_ba or not histories) and model["points"]:
         P[order], hist, _ = eng.bundle(order, P, model, **ba)
         histories.append(hist)
         model = eng.round(registered, P)
         rounds += 1
     out = eng.result(model)
+    if calibrate is not None:
+        out.update(K=calibrated["K"] if calibrated else K.copy(), dist=calibrated["dist"] if calibrated else np.asarray((0.0, 0.0) if calibrate.get("dist") is None else calibrate["dist"], np.float64).reshape(2))
     P_out = np.full((n_img, 3, 4), np.nan)
     P_out[order] = P[order]
     out.update(P=P_out, registered=registered.astype(bool), order=np.array(order, np.int32), tries=tries, steps=steps, seeds=seeds,
@@ -443,7 +463,7 @@ def register_loop(eng, n_img, pairs, K, seed_pair=None, min_corr=MIN_CORR, min_s
 
 def register_tracks(store, n_query, pairs, keypoints, K, frame_size, ratio=0.70, keep=None, seed_pair=None, min_len=2, max_len=None, huber=1.0,
                     obs_thresh=2.0, max_reproj=2.0, min_angle_deg=2.0, refine_iters=10, grid=8, min_corr=MIN_CORR, min_seed=MIN_SEED, seed_tries=5,
-                    max_tries=2, pnp=None, ba_every=BA_EVERY, ba=None, log=None, pair_config=None):
+                    max_tries=2, pnp=None, ba_every=BA_EVERY, ba=None, log=None, pair_config=None, calibrate=None):
     """Cameras of unordered images from their all-pairs matches.  store, n_query, pairs as `sharded.match_pairs_sharded` returns and takes
     them; keypoints: list over images of [n_i, 2] float32 device tensors, 2 to 4 096 images (the four kernels take 65 536; the seed
     order is counted by sfm_view_pair_counts, which takes 4 096); K 3 x 3 (one camera model); frame_size (width, height).  SfmHipError
@@ -473,6 +493,10 @@ def register_tracks(store, n_query, pairs, keypoints, K, frame_size, ratio=0.70,
     (tests/test_gpu_tracks_register.py, scene 4); `densify_tracks` plans a depth map per row of P and is not exercised on NaN rows: keep
     the registered images and renumber cam_idx before it.
 
+    calibrate: None (the code path above exactly), or dict(free=("f", "k1"), dist=None): the FINAL adjustment is
+    `track_cal.bundle_adjust_calibrated` (docs/tracks.md §15) and always runs; the rows of P are built with K', and the result gains
+    "K" (3 x 3) and "dist" (k1, k2).  The registration rounds and the adjustments before it use the K given here.
+
     Host waits outside the solvers (E-RANSAC / recoverPose, PnP) and the bundle adjustment: the tracks' one per batch of labelling
     rounds, ONE read of the shared-track counts, ONE read per model round (a seed candidate, a registration, a bundle adjustment and the
     end cost one round each; a failed PnP costs none), and ONE download at the end."""
@@ -482,6 +506,8 @@ def register_tracks(store, n_query, pairs, keypoints, K, frame_size, ratio=0.70,
     if len(keypoints) > MAX_IMAGES:
         raise SfmHipError(f"register_tracks: {len(keypoints)} images exceed {MAX_IMAGES}, the limit of sfm_view_pair_counts, which counts the "
                           "tracks two images share for the seed order")
+    if calibrate is not None and sorted(set(calibrate) - {"free", "dist"}):
+        raise SfmHipError(f"register_tracks: calibrate takes free and dist, not {sorted(set(calibrate) - {'free', 'dist'})}")
     eng = _HipEngine(store, n_query, pairs, keypoints, K, frame_size, ratio, keep, min_len, max_len, huber, obs_thresh, max_reproj, min_angle_deg,
                      refine_iters, grid)
-    return register_loop(eng, len(keypoints), pairs, K, seed_pair, min_corr, min_seed, seed_tries, max_tries, pnp, ba_every, ba, log, pair_config)
+    return register_loop(eng, len(keypoints), pairs, K, seed_pair, min_corr, min_seed, seed_tries, max_tries, pnp, ba_every, ba, log, pair_config, calibrate)

@@ -326,14 +326,30 @@ def _robust_result(host_head, lowered, pruned, img_off, kp):
                 status=np.array([int(host_head[6]), lowered], np.int32), tracks_dropped=int(host_head[10]), obs_dropped=int(host_head[11]))
 
 
-def adjust_tracks(result, P, K, device=None, **kw):
+def adjust_tracks(result, P, K, device=None, calibrate=None, **kw):
     """Bundle adjustment of the tracks `run_tracks` returned (either variant) from the cameras P [n_img, 3, 4] it was given, K 3 x 3:
     `track_ba.bundle_adjust_tracks(cams_from_P(P, K), K, points, obs, cam_idx, pt_idx, **kw)` (huber, iters, lam, fix_first_camera,
     cg_tol, cg_iters, log).  Returns (P' [n_img, 3, 4] float64, points' [T, 3] float64, info) on the host; info holds the history of
-    robust costs and the counts of the last sweep.  `run_tracks(..., P')` then runs on the adjusted cameras."""
+    robust costs and the counts of the last sweep.  `run_tracks(..., P')` then runs on the adjusted cameras.
+    calibrate: None, or dict(free=("f", "k1"), dist=None): `track_cal.bundle_adjust_calibrated` instead (docs/tracks.md §15), the
+    intrinsics named in `free` among the unknowns, from K and dist = (k1, k2).  P' is then built with K', and info gains "K"
+    (3 x 3) and "dist" (k1, k2): the keypoints are pixels of the DISTORTED camera, `track_cal.undistort_points` maps them to the
+    pinhole camera K' that P' describes."""
     from . import track_ba
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     cams0 = track_ba.cams_from_P(P, K)
+    if calibrate is not None:
+        from . import track_cal
+        unknown = sorted(set(calibrate) - {"free", "dist"})
+        if unknown:
+            raise SfmHipError(f"adjust_tracks: calibrate takes free and dist, not {unknown}")
+        cams, X, K_new, dist, hist, info = track_cal.bundle_adjust_calibrated(
+            _upload(cams0, dev), K, calibrate.get("dist"), _upload(np.asarray(result["points"], np.float64).reshape(-1, 3), dev),
+            _upload(np.asarray(result["obs"], np.float32).reshape(-1, 2), dev), _upload(np.asarray(result["cam_idx"], np.int32), dev),
+            _upload(np.asarray(result["pt_idx"], np.int32), dev), free=calibrate.get("free", ("f", "k1")), **kw)
+        host = torch.cat([cams.reshape(-1), X.reshape(-1)]).cpu().numpy()
+        info = dict(info, history=hist, K=K_new, dist=dist)
+        return track_ba.P_from_cams(host[:cams.numel()].reshape(-1, 6), K_new), host[cams.numel():].reshape(-1, 3).copy(), info
     cams, X, hist, info = track_ba.bundle_adjust_tracks(_upload(cams0, dev), K, _upload(np.asarray(result["points"], np.float64).reshape(-1, 3), dev),
                                                         _upload(np.asarray(result["obs"], np.float32).reshape(-1, 2), dev),
                                                         _upload(np.asarray(result["cam_idx"], np.int32), dev),
@@ -343,13 +359,19 @@ def adjust_tracks(result, P, K, device=None, **kw):
     return track_ba.P_from_cams(host[:cams.numel()].reshape(-1, 6), K), host[cams.numel():].reshape(-1, 3).copy(), info
 
 
-def densify_tracks(result, images, K, P, points=None, nsrc=4, min_angle_deg=None, max_angle_deg=None, min_good=None, lo=2, hi=98, device=None, **kw):
+def densify_tracks(result, images, K, P, points=None, nsrc=4, min_angle_deg=None, max_angle_deg=None, min_good=None, lo=2, hi=98, device=None, dist=None,
+                   **kw):
     """Dense reconstruction of the views of a `run_tracks` result (either variant): `track_ba.plan` -> `mvs_plan.plan_views` ->
     `mvs_plan.host_plan` -> `mvs.run_mvs(images, K, posearr, points, neighbours=..., ranges=..., **kw)`.  P [n_img, 3, 4] float64 and
     `points` (default result["points"]; pass the float64 points `adjust_tracks` returned with its P') are the cameras and the cloud the
     plan is made from; the angle window and min_good default to mvs_plan's.  Returns run_mvs's dict plus "plan" (host_plan's dict).
-    Host waits: host_plan's one, then run_mvs's."""
+    Host waits: host_plan's one, then run_mvs's.
+    dist: None, or (k1, k2) of the camera that took `images` (`adjust_tracks(calibrate=...)` returns it with K' in info): the frames
+    are undistorted on the device with the K given here (`track_cal.undistort_images`, one batched call when they share a size)
+    before `run_mvs` sees them; pixels whose source lies outside the frame are black.  P stays as it is."""
     from . import mvs, mvs_plan, track_ba
+    if dist is not None:
+        images = _undistorted(images, K, dist, torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     K = np.asarray(K, np.float64).reshape(3, 3)
     P = np.ascontiguousarray(np.asarray(P, np.float64).reshape(-1, 3, 4))
@@ -364,6 +386,20 @@ def densify_tracks(result, images, K, P, points=None, nsrc=4, min_angle_deg=None
     out = mvs.run_mvs(images, K, posearr, X, nsrc=nsrc, neighbours=hp["neighbours"], ranges=hp["ranges"], **kw)
     out["plan"] = hp
     return out
+
+
+def _undistorted(images, K, dist, dev):
+    """The frames as device tensors, undistorted: one batched call when they share a shape, else one call per frame; no host wait."""
+    from . import track_cal
+    frames = [(im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im))).to(dev).contiguous() for im in images]
+    if not frames:
+        return frames
+    if all(f.shape == frames[0].shape for f in frames):
+        stack = torch.stack(frames).contiguous()
+        if stack.dim() == 3:                                            # gray frames [n, H, W]
+            return list(track_cal.undistort_images(stack.unsqueeze(-1).contiguous(), K, dist).squeeze(-1))
+        return list(track_cal.undistort_images(stack, K, dist))
+    return [track_cal.undistort_images(f if f.dim() == 3 else f.unsqueeze(-1).contiguous(), K, dist).reshape(f.shape) for f in frames]
 
 
 def verify_keep(store, n_query, pairs, keypoints, K, ratio=0.70, batched=False, **kw):
